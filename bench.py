@@ -27,7 +27,13 @@ bit-exactly against the CPU parallel_fft, and at N > 1 every rank's block of
 the distributed NTT (SHA-256 digests) against the same parallel_fft.  Rank 0
 at N=1 also times the CPU restatements as the baseline.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; N > 1 under
+A plain run does only what `value` needs: set-up, the warm-up and the K timed
+MSM steps (`ms_per_step`), then the line; --dump-outputs DIR also writes the
+last timed step's result (dump_outputs).  The NTT legs, the checks, the CPU
+baseline and every other leg described here run under --full, after the timed
+MSM steps, and their fields are null in a plain run's line.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]; N > 1 under
 torch.distributed.run (one process per GPU), or plain `python bench.py --gpus N`,
 which starts the N rank processes itself (launch_ranks) with the same
 environment the launcher gives them.
@@ -116,6 +122,12 @@ def parse(argv=None):
     ap.add_argument("--msm-log", type=int, default=26)
     ap.add_argument("--ntt-log", type=int, default=24)
     ap.add_argument("--curve", default="bls12_381")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed MSM steps also run every other leg: the unprepared-bases and "
+                         "window-table MSMs, the NTT legs, the oracle checks, the CPU baseline, the end-to-end "
+                         "API timings and the side lines (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64, see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the oracle checks (profiling runs)")
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -213,6 +225,17 @@ def omega_for(cid: int, r_int: int, ln: int) -> np.ndarray:
 def block_digests(a: np.ndarray, world: int) -> list:
     m = a.shape[0] // world
     return [hashlib.sha256(np.ascontiguousarray(a[r * m:(r + 1) * m]).tobytes()).hexdigest() for r in range(world)]
+
+
+def dump_outputs(path: str, msm_result: np.ndarray) -> None:
+    """--dump-outputs: what the caller of the timed path received in the last
+    timed step, one .npy per array.  msm_result.npy: the MSM's Jacobian point
+    [X, Y, Z] (3 x Fq limbs, Montgomery form) as the step returned it, cut into
+    its 32-bit words (little-endian order within each 64-bit limb), each word
+    held exactly in a float64."""
+    os.makedirs(path, exist_ok=True)
+    words = np.ascontiguousarray(msm_result, dtype="<u8").view("<u4")
+    np.save(os.path.join(path, "msm_result.npy"), words.astype(np.float64))
 
 
 def _free_port() -> int:
@@ -346,9 +369,10 @@ def main():
     log_n = args.ntt_log
     n_ntt = 1 << log_n
     omega_m = omega_for(cid, r_int, log_n)
-    # any value < r is a Montgomery form; every rank holds the same seeded input
-    ntt_in = rand_scalars(np.random.default_rng([NTT_SEED, 0]), n_ntt, r_int)
-    d_ntt = ecgpu.DeviceBuffer.upload(prog, ntt_in)
+    if args.full:
+        # any value < r is a Montgomery form; every rank holds the same seeded input
+        ntt_in = rand_scalars(np.random.default_rng([NTT_SEED, 0]), n_ntt, r_int)
+        d_ntt = ecgpu.DeviceBuffer.upload(prog, ntt_in)
 
     def ntt_step():
         # in place; back-to-back steps transform the previous output (still uniform Fr data)
@@ -380,9 +404,12 @@ def main():
     if comm is not None:  # the last step's status + partial all-gather, slowest rank
         comm["msm_allgather_us"] = group.max(edist.last_exchange_us(prog))
     msm_result = result.copy()
+    if args.dump_outputs and rank == 0:  # every rank holds the same folded result
+        dump_outputs(args.dump_outputs, msm_result)
+    # Everything from here to the report is behind --full: a plain run stops at the headline figure.
     # the same MSM over the [x, y] bases, converting them inside the step (reported, not `value`)
     unprep_ms = None
-    if not args.unprepared:
+    if args.full and not args.unprepared:
         msm_step(d_bases)
         barrier()
         t0 = time.perf_counter()
@@ -396,7 +423,7 @@ def main():
     # the same MSM over a window table of the bases (fixed-base form, ecg_msm_prepare_table): reported
     # beside `value`, which stays on the per-call base layout the reference's API takes
     table = None
-    if not args.no_table and not args.unprepared and cid in (0, 1) and not grid:
+    if args.full and not args.no_table and not args.unprepared and cid in (0, 1) and not grid:
         msm_prep = d_msm_bases
         t0 = time.perf_counter()
         d_tab = ecgpu.prepare_bases(prog, args.curve, d_bases, n_loc, window_table=0)
@@ -417,25 +444,26 @@ def main():
         del msm_prep
 
     # ------------------------------------------------------------ NTT timing (one transform per GPU)
-    for _ in range(args.warmup):
-        ntt_step()
-    barrier()
-    t0 = time.perf_counter()
-    pass_ms, pass_launch = 0.0, 0
-    for _ in range(args.steps):
-        ntt_step()
-        ms, cnt = prog.kernel_time("ntt_pass")
-        pass_ms += ms
-        pass_launch += cnt
-    barrier()
-    ntt_s = group.max(time.perf_counter() - t0) / args.steps
-    pass_avg_ms = group.max(pass_ms / max(pass_launch, 1))
-    passes_per_ntt = pass_launch / args.steps
+    if args.full:
+        for _ in range(args.warmup):
+            ntt_step()
+        barrier()
+        t0 = time.perf_counter()
+        pass_ms, pass_launch = 0.0, 0
+        for _ in range(args.steps):
+            ntt_step()
+            ms, cnt = prog.kernel_time("ntt_pass")
+            pass_ms += ms
+            pass_launch += cnt
+        barrier()
+        ntt_s = group.max(time.perf_counter() - t0) / args.steps
+        pass_avg_ms = group.max(pass_ms / max(pass_launch, 1))
+        passes_per_ntt = pass_launch / args.steps
 
     # ------------------------------------------------------------ distributed NTT (N > 1): one 2^24 over all ranks
     ntt_dist = None
     dist_digests = None
-    if world > 1:
+    if args.full and world > 1:
         m = n_ntt // world
         d_blk = ecgpu.DeviceBuffer.upload(prog, ntt_in[rank * m:(rank + 1) * m])
         for _ in range(args.warmup):
@@ -461,7 +489,7 @@ def main():
     # timed CPU baseline, never on the measured path.
     checks = {}
     cpu_baseline = None
-    if rank == 0 and not args.no_check:
+    if args.full and rank == 0 and not args.no_check:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import coracle as co
 
@@ -505,7 +533,7 @@ def main():
     # The reference API takes host slices and copies them in and out on every
     # call (multiexp.rs:163-164, fft.rs:89,129).  Not `value`: DESIGN.md §6.
     e2e = None
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         host_bases = d_bases.read(shape=(n_loc, 2 * lq))
         kern = ecgpu.MultiexpKernel.create([prog], [], args.curve)
         pool = ecgpu.Worker()
@@ -554,7 +582,7 @@ def main():
 
     # ------------------------------------------------------------ side lines (N = 1): SURVEY §8f rows
     aux = None
-    if rank == 0 and world == 1 and not args.no_aux:
+    if args.full and rank == 0 and world == 1 and not args.no_aux:
         aux = {}
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import coracle as co20  # checker only (KAT / inputs), never timed
@@ -818,7 +846,6 @@ def main():
                 ntt_traffic, ntt_src = d_bn["ntt_traffic_gb_per_launch"], d_bn["ntt_source"]
         except (OSError, ValueError, KeyError, TypeError) as e:
             print(f"bench: ignoring {bn}: {type(e).__name__}: {e}", file=sys.stderr)
-    ntt_achieved = 64 * n_ntt / (pass_avg_ms / 1e3) / 1e9
     roofline = {"bound": "valu", "kernel": "msm_accumulate", "avg_ms": acc_avg_ms,
                 "traffic": acc_traffic, "traffic_unit": "GB/launch", "traffic_source": acc_src}
     if W and cid in RR_LIMBS:
@@ -866,13 +893,7 @@ def main():
         "msm_ms_unprepared_bases": unprep_ms,
         "msm_window_table": table,
         "roofline": roofline,
-        "ntt": {"metric": f"Fr NTT elements/sec @2^{log_n}", "value": world * n_ntt / ntt_s,
-                "unit": "elements/s", "ms_per_ntt": ntt_s * 1e3, "scaling": "weak (one transform per GPU)",
-                "ms_kernels_per_ntt": pass_ms / args.steps, "passes": passes_per_ntt,
-                "roofline": {"bound": "valu", "achieved": ntt_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": ntt_achieved / HBM_PEAK_GBS, "traffic": ntt_traffic,
-                             "traffic_unit": "GB/launch", "traffic_source": ntt_src, "kernel": "ntt_pass",
-                             "avg_ms": pass_avg_ms, "note": "HBM fraction of a VALU-bound pass (64 B/element)"}},
+        "ntt": None,  # the NTT legs run under --full
         "ntt_dist": ntt_dist,
         "rccl": comm,
         "checks": checks,
@@ -881,13 +902,23 @@ def main():
         "aux": aux,
         "runtime": runtime,
     }
-    muls = ntt_fr_muls(log_n)
-    # reduced-radix Fr product (fieldrr.hpp, 9 x 29-bit limbs): 81 schoolbook + 81 reduction mads
-    mad_rate = muls * FR_RR_MADS[cid] / (pass_ms / args.steps / 1e3) / 1e12
-    line["ntt"]["valu"] = {"kernel": "ntt_pass", "achieved": mad_rate, "peak": MAD_PEAK_T,
-                           "unit": "T v_mad_u64_u32/s", "frac": mad_rate / MAD_PEAK_T,
-                           "note": f"{muls / n_ntt:.2f} Fr products per element per transform x {FR_RR_MADS[cid]} "
-                                   "v_mad_u64_u32 / kernel time; peak as the MSM roofline's"}
+    if args.full:
+        ntt_achieved = 64 * n_ntt / (pass_avg_ms / 1e3) / 1e9
+        muls = ntt_fr_muls(log_n)
+        # reduced-radix Fr product (fieldrr.hpp, 9 x 29-bit limbs): 81 schoolbook + 81 reduction mads
+        mad_rate = muls * FR_RR_MADS[cid] / (pass_ms / args.steps / 1e3) / 1e12
+        line["ntt"] = {
+            "metric": f"Fr NTT elements/sec @2^{log_n}", "value": world * n_ntt / ntt_s,
+            "unit": "elements/s", "ms_per_ntt": ntt_s * 1e3, "scaling": "weak (one transform per GPU)",
+            "ms_kernels_per_ntt": pass_ms / args.steps, "passes": passes_per_ntt,
+            "roofline": {"bound": "valu", "achieved": ntt_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": ntt_achieved / HBM_PEAK_GBS, "traffic": ntt_traffic,
+                         "traffic_unit": "GB/launch", "traffic_source": ntt_src, "kernel": "ntt_pass",
+                         "avg_ms": pass_avg_ms, "note": "HBM fraction of a VALU-bound pass (64 B/element)"},
+            "valu": {"kernel": "ntt_pass", "achieved": mad_rate, "peak": MAD_PEAK_T,
+                     "unit": "T v_mad_u64_u32/s", "frac": mad_rate / MAD_PEAK_T,
+                     "note": f"{muls / n_ntt:.2f} Fr products per element per transform x {FR_RR_MADS[cid]} "
+                             "v_mad_u64_u32 / kernel time; peak as the MSM roofline's"}}
     print(json.dumps(line))
     group.barrier()
     group.close()

@@ -211,7 +211,7 @@ def _install_device_fakes(rank, world, corrupt=False, fail_rank=None):
     return side
 
 
-def _bench_main_worker(rank, world, port, q, corrupt=False, fail_rank=None, extra=()):
+def _bench_main_worker(rank, world, port, q, corrupt=False, fail_rank=None, extra=(), full=True):
     import contextlib
     import io
 
@@ -225,8 +225,8 @@ def _bench_main_worker(rank, world, port, q, corrupt=False, fail_rank=None, extr
     import bench
     import ecgpu
 
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--msm-log", "10",
-                "--ntt-log", "8", *extra]
+    sys.argv = ["bench.py", *(["--full"] if full else []), "--gpus", str(world), "--steps", "2", "--warmup", "1",
+                "--msm-log", "10", "--ntt-log", "8", *extra]
     out = io.StringIO()
     try:
         with contextlib.redirect_stdout(out):
@@ -270,6 +270,43 @@ def test_bench_main_world2(corrupt):
     assert line["rccl"] == {"transport": ["rccl"], "count": [2], "ranks": [0, 1],
                             "devices": ["0000:11:00.0", "0000:21:00.0"], "distinct": True,
                             "msm_allgather_us": 41.0}
+
+
+@pytest.mark.timeout(300)
+def test_bench_main_world2_plain_run_dumps_its_result(tmp_path):
+    """bench.main() at N = 2 without --full: only the timed MSM steps run (every
+    other leg's field is empty), and --dump-outputs writes the last step's
+    Jacobian point as exact 32-bit words in float64 -- the known answer."""
+    import multiprocessing as mp
+
+    sys.path.insert(0, ROOT)
+    import bench
+    import coracle as co
+
+    port = _free_port()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    extra = ("--dump-outputs", str(tmp_path / "dump"))
+    procs = [ctx.Process(target=_bench_main_worker, args=(r, 2, port, q, False, None, extra, False)) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(240)
+    outs = dict(q.get(timeout=10) for _ in range(2))
+    assert all(p.exitcode == 0 for p in procs)
+    line = json.loads(outs[0].strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx((1 << 10) / (line["ms_per_step"] / 1e3))
+    for leg in ("msm_ms_unprepared_bases", "msm_window_table", "ntt", "ntt_dist", "cpu_baseline", "e2e_api", "aux"):
+        assert line[leg] is None, leg
+    assert line["checks"] == {}
+    assert os.listdir(tmp_path / "dump") == ["msm_result.npy"]
+    words = np.load(tmp_path / "dump" / "msm_result.npy")
+    assert words.dtype == np.float64 and words.shape == (36,)
+    assert (words == np.floor(words)).all() and words.min() >= 0 and words.max() < 2.0 ** 32
+    got = np.ascontiguousarray(words.astype("<u4")).view("<u8")
+    want = co.gen_mul(0, bench.msm_kat_scalar(co, 0, 2, 1 << 10, bench.R_BLS, 2))
+    assert (co.jac_to_affine(0, got) == co.jac_to_affine(0, want)).all()
 
 
 @pytest.mark.timeout(300)
@@ -349,7 +386,7 @@ def _run_self_launch(world, extra_env=None, timeout=280):
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update({"OMP_NUM_THREADS": "2", **(extra_env or {})})
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_fake_ranks.py"), "--gpus", str(world),
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_fake_ranks.py"), "--full", "--gpus", str(world),
            "--steps", "2", "--warmup", "1", "--msm-log", "10", "--ntt-log", "8"]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 

@@ -1,6 +1,7 @@
-# One entry point for GPU-box work (run under gpurun from the repo root).
+# One entry point for work on the MI355X host (run from the repo root).  Logs, traces and
+# counter CSVs go to $ECG_OUT (default: out/ in the repo root; tools/pmc_summary.py reads the same).
 #   bash tools/gpu.sh tests [pytest args]     -m gpu parity suite (+ smoke)
-#   bash tools/gpu.sh bench [bench args]      one bench.py line -> gpurun_out/bench.log
+#   bash tools/gpu.sh bench [bench args]      one bench.py --full line -> $ECG_OUT/bench.log
 #   bash tools/gpu.sh prof TAG                rocprofv3 kernel stats + FETCH/WRITE PMC passes
 #   bash tools/gpu.sh sq TAG LOGN [COUNTERS]  one SQ counter pass over tools/msm_once.py
 #   bash tools/gpu.sh round TAG               tests + smoke + bench + bn254 bench + prof
@@ -8,53 +9,54 @@
 # first failure ends the call.
 set -o pipefail
 R=$PWD
-mkdir -p $R/gpurun_out
+OUT=${ECG_OUT:-$R/out}
+mkdir -p $OUT
 cmd=${1:-tests}; shift || true
 
 tests() {
   timeout -k 10 1200 python3 -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread "$@" \
-    > $R/gpurun_out/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $R/gpurun_out/pytest_gpu.log
+    > $OUT/pytest_gpu.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $OUT/pytest_gpu.log
   [ $rc -eq 0 ] || return $rc
-  timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $R/gpurun_out/smoke.log 2>&1; rc=$?
-  echo "smoke rc=$rc"; tail -2 $R/gpurun_out/smoke.log
+  timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
+  echo "smoke rc=$rc"; tail -2 $OUT/smoke.log
   return $rc
 }
 
 bench() {
-  timeout -k 10 600 python3 bench.py "$@" > $R/gpurun_out/bench.log 2>&1; rc=$?
-  echo "bench rc=$rc"; tail -1 $R/gpurun_out/bench.log | cut -c1-1500
+  timeout -k 10 600 python3 bench.py --full "$@" > $OUT/bench.log 2>&1; rc=$?
+  echo "bench rc=$rc"; tail -1 $OUT/bench.log | cut -c1-1500
   return $rc
 }
 
 prof() {
   local TAG=$1
   ( cd /tmp && export TMPDIR=/tmp &&
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$TAG -o run --output-format csv \
-      -- python3 $R/bench.py --no-cpu-baseline --no-e2e --no-aux --no-table > $R/gpurun_out/prof_${TAG}_bench.log 2>&1 &&
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$TAG -o run --output-format csv \
+      -- python3 $R/bench.py --full --no-cpu-baseline --no-e2e --no-aux --no-table > $OUT/prof_${TAG}_bench.log 2>&1 &&
     echo trace-ok &&
-    timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $R/gpurun_out/pmc_fetch_$TAG -o run \
-      --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-e2e --no-aux --no-table --steps 1 --warmup 0 \
-      > $R/gpurun_out/pmc_fetch_${TAG}.log 2>&1 && echo fetch-ok &&
-    timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $R/gpurun_out/pmc_write_$TAG -o run \
-      --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-e2e --no-aux --no-table --steps 1 --warmup 0 \
-      > $R/gpurun_out/pmc_write_${TAG}.log 2>&1 && echo write-ok )
+    timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch_$TAG -o run \
+      --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-e2e --no-aux --no-table --steps 1 --warmup 0 \
+      > $OUT/pmc_fetch_${TAG}.log 2>&1 && echo fetch-ok &&
+    timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write_$TAG -o run \
+      --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-e2e --no-aux --no-table --steps 1 --warmup 0 \
+      > $OUT/pmc_write_${TAG}.log 2>&1 && echo write-ok )
 }
 
 sq() {
   local TAG=$1 LOGN=$2
   local CTRS=${3:-"SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY"}
   ( cd /tmp && export TMPDIR=/tmp &&
-    timeout -s KILL 300 rocprofv3 --pmc $CTRS --kernel-trace -d $R/gpurun_out/sq_$TAG -o run --output-format csv \
-      -- python3 $R/tools/msm_once.py $LOGN 1 > $R/gpurun_out/sq_$TAG.log 2>&1 ) || { echo "sq $TAG failed"; return 1; }
-  python3 $R/tools/sq_summary.py $R/gpurun_out/sq_$TAG/run_counter_collection.csv | tee $R/gpurun_out/sq_${TAG}_summary.txt
+    timeout -s KILL 300 rocprofv3 --pmc $CTRS --kernel-trace -d $OUT/sq_$TAG -o run --output-format csv \
+      -- python3 $R/tools/msm_once.py $LOGN 1 > $OUT/sq_$TAG.log 2>&1 ) || { echo "sq $TAG failed"; return 1; }
+  python3 $R/tools/sq_summary.py $OUT/sq_$TAG/run_counter_collection.csv | tee $OUT/sq_${TAG}_summary.txt
 }
 
 # one counter pass over any python target: pmc TAG "CTR ..." script.py args...
 pmc() {
   local TAG=$1 CTRS=$2; shift 2
   ( cd /tmp && export TMPDIR=/tmp &&
-    timeout -s KILL 300 rocprofv3 --pmc $CTRS --kernel-trace -d $R/gpurun_out/pmc_$TAG -o run --output-format csv \
-      -- python3 "$@" > $R/gpurun_out/pmc_$TAG.log 2>&1 ) || { echo "pmc $TAG failed"; return 1; }
+    timeout -s KILL 300 rocprofv3 --pmc $CTRS --kernel-trace -d $OUT/pmc_$TAG -o run --output-format csv \
+      -- python3 "$@" > $OUT/pmc_$TAG.log 2>&1 ) || { echo "pmc $TAG failed"; return 1; }
   echo "pmc $TAG ok"
 }
 
@@ -91,7 +93,7 @@ case $cmd in
   round)
     TAG=$1
     tests && bench && {
-      timeout -k 10 600 python3 bench.py --curve bn254 --no-e2e > $R/gpurun_out/bench_bn254.log 2>&1; rc=$?
+      timeout -k 10 600 python3 bench.py --full --curve bn254 --no-e2e > $OUT/bench_bn254.log 2>&1; rc=$?
       echo "bn254 bench rc=$rc"; [ $rc -eq 0 ]; } && prof $TAG ;;
   *) echo "unknown subcommand $cmd"; exit 2 ;;
 esac

@@ -11,11 +11,12 @@ from collections import defaultdict
 
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+run_dir = os.environ.get("ECG_OUT") or os.path.join(root, "out")  # where tools/gpu.sh prof wrote
 out_dir = os.path.join(root, "profiles", tag)
 os.makedirs(out_dir, exist_ok=True)
 res = defaultdict(dict)
 for ctr, sub in (("FETCH_SIZE", f"pmc_fetch_{tag}"), ("WRITE_SIZE", f"pmc_write_{tag}")):
-    path = os.path.join(root, "gpurun_out", sub, "run_counter_collection.csv")
+    path = os.path.join(run_dir, sub, "run_counter_collection.csv")
     acc = defaultdict(lambda: [0.0, 0])
     with open(path) as f:
         for row in csv.DictReader(f):
@@ -34,7 +35,7 @@ with open(os.path.join(out_dir, "pmc_fetch_write.json"), "w") as f:
 # the copy bench.py reads on the GPU box (profiles/r*/ stays out of the gpurun push)
 with open(os.path.join(root, "profiles", "pmc_current.json"), "w") as f:
     json.dump({"source": f"profiles/{tag}/pmc_fetch_write.json", "kernels": res}, f, indent=1, sort_keys=True)
-stats = os.path.join(root, "gpurun_out", f"prof_{tag}", "run_kernel_stats.csv")
+stats = os.path.join(run_dir, f"prof_{tag}", "run_kernel_stats.csv")
 if os.path.exists(stats):
     shutil.copy(stats, os.path.join(out_dir, "kernel_stats.csv"))
 for k in ("msm_accumulate", "ntt_pass"):
