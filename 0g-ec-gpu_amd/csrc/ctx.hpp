@@ -75,6 +75,19 @@ struct ecg_ctx {
   int tw_full = 0;
   uint32_t tw_log_n = 0;
   uint64_t tw_omega[4] = {0, 0, 0, 0};
+  // table sets of the shifted / scaled transform (ntt_ext.hip): three slots,
+  // least recently used replaced first; slot i owns the workspace buffers
+  // "ntt_ext_twf<i>" and "ntt_ext_pq<i>".  key = omega | in_shift | out_shift |
+  // scale (absent parameters zero, `present` says which are there).
+  struct NttExtSlot {
+    int fid = -1;
+    uint32_t log_n = 0;
+    int present = 0;
+    uint64_t key[16] = {0};
+    uint64_t used = 0;  // tw_ext_clock at the last use
+  };
+  NttExtSlot tw_ext[3];
+  uint64_t tw_ext_clock = 0;
   // persistent base cache: converted [x, y] bases keyed by the
   // caller's host buffer, reused while the same (pointer, size, curve,
   // layout) comes back -- the reference's Arc<Vec<G>> bases are immutable.
@@ -148,6 +161,14 @@ int ntt_validate(int field_id, uint32_t log_n);
 // batch: that many same-size transforms with the same omega, back to back at d_data
 int ntt_run(ecg_ctx* ctx, int field_id, void* d_data, const uint64_t* omega, uint32_t log_n,
             hipStream_t s, ecg_abort_cb abort_cb, void* user, uint32_t batch = 1);
+// ntt_ext.hip: y[k] = scale out_shift^k sum_j in_shift^j a[j] omega^(jk); a
+// null parameter is 1, all three null is ntt_run.  ntt_ex_validate checks the
+// field, log_n and the parameters (before any allocation or copy).
+int ntt_ex_validate(int field_id, uint32_t log_n, const uint64_t* in_shift, const uint64_t* out_shift,
+                    const uint64_t* scale);
+int ntt_run_ex(ecg_ctx* ctx, int field_id, void* d_data, const uint64_t* omega, uint32_t log_n,
+               const uint64_t* in_shift, const uint64_t* out_shift, const uint64_t* scale, hipStream_t s,
+               ecg_abort_cb abort_cb, void* user);
 // MSM / point-sum results are written to HOST memory (3 x Lq u64, normalised
 // Jacobian): the last serial steps (window fold, normalisation) run on the host.
 // scalar_mont: scalars are Montgomery Fr elements (converted on device).

@@ -308,6 +308,46 @@ int ecg_fft(ecg_ctx* ctx, int field_id, uint64_t* inout, const uint64_t* omega, 
   return kt_collect(ctx);
 }
 
+// Shifted / scaled transform (ntt_ext.hip); all three parameters null = ecg_fft_dev / ecg_fft.
+int ecg_fft_dev_ex(ecg_ctx* ctx, int field_id, void* d_inout, const uint64_t* omega, uint32_t log_n,
+                   const uint64_t* in_shift, const uint64_t* out_shift, const uint64_t* scale, void* stream) {
+  if (!in_shift && !out_shift && !scale) return ecg_fft_dev(ctx, field_id, d_inout, omega, log_n, stream);
+  ECG_ENTER(ctx);
+  if (!d_inout || !omega) {
+    set_error("ecg_fft_dev_ex: null pointer");
+    return ECG_ERR_INVALID;
+  }
+  hipStream_t s = pick_stream(ctx, stream);
+  ECG_TRY(ntt_run_ex(ctx, field_id, d_inout, omega, log_n, in_shift, out_shift, scale, s, nullptr, nullptr));
+  ECG_HIP(hipStreamSynchronize(s));
+  return kt_collect(ctx);
+}
+
+int ecg_fft_ex(ecg_ctx* ctx, int field_id, uint64_t* inout, const uint64_t* omega, uint32_t log_n,
+               const uint64_t* in_shift, const uint64_t* out_shift, const uint64_t* scale, ecg_abort_cb abort_cb,
+               void* user) {
+  if (!in_shift && !out_shift && !scale) return ecg_fft(ctx, field_id, inout, omega, log_n, abort_cb, user);
+  ECG_ENTER(ctx);
+  if (!inout || !omega) {
+    set_error("ecg_fft_ex: null pointer");
+    return ECG_ERR_INVALID;
+  }
+  ECG_TRY(ntt_ex_validate(field_id, log_n, in_shift, out_shift, scale));  // before any allocation or copy
+  const size_t bytes = ((size_t)1 << log_n) * fr_bytes(field_id);
+  void* d;
+  ECG_TRY(ws_get(ctx, "fft_io", bytes, &d));
+  hipStream_t s = ctx->stream;
+  ECG_HIP(hipMemcpyAsync(d, inout, bytes, hipMemcpyHostToDevice, s));
+  int rc = ntt_run_ex(ctx, field_id, d, omega, log_n, in_shift, out_shift, scale, s, abort_cb, user);
+  if (rc != ECG_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  ECG_HIP(hipMemcpyAsync(inout, d, bytes, hipMemcpyDeviceToHost, s));
+  ECG_HIP(hipStreamSynchronize(s));
+  return kt_collect(ctx);
+}
+
 // Same-size transforms with the same omega, back to back in one device buffer
 // and run as ONE batched transform (each pass launches every transform's
 // tiles together): a 2^16 transform alone is 64 workgroups on 256 CUs.
@@ -1002,6 +1042,7 @@ int ecg_ctx_release_workspace(ecg_ctx* ctx) {
     if (kv.second.ptr) ECG_HIP(hipFree(kv.second.ptr));
   ctx->ws.clear();
   ctx->tw_fid = -1;  // the NTT's twiddle tables lived in the workspace
+  for (auto& e : ctx->tw_ext) e = ecg_ctx::NttExtSlot();
   return ECG_OK;
 }
 

@@ -85,6 +85,11 @@ _SIGS = {
                                     ctypes.POINTER(_u64p), _u64p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
                                     ABORT_CB, ctypes.c_void_p]),
     "ecg_fft_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, _u64p, ctypes.c_uint32, ctypes.c_void_p]),
+    "ecg_fft_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, ctypes.c_uint32, _u64p, _u64p, _u64p,
+                                  ABORT_CB, ctypes.c_void_p]),
+    "ecg_fft_dev_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, _u64p, ctypes.c_uint32, _u64p,
+                                      _u64p, _u64p, ctypes.c_void_p]),
+    "ecg_fft_set_fused": (ctypes.c_int, [ctypes.c_int]),
     "ecg_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
     "ecg_msm_multi": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, _u64p, _u64p,
                                      ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
@@ -551,11 +556,18 @@ def prepare_bases(prog: Program, curve, d_bases: DeviceBuffer, n: int, window_ta
     return PreparedBases(prog, p, cid, n, window_table=int(window_table) or -1)
 
 
-def fft_dev(prog: Program, field, d_data: DeviceBuffer, omega: np.ndarray, log_n: int) -> None:
-    """In-place NTT of HBM-resident data (ecg_fft_dev)."""
+def fft_dev(prog: Program, field, d_data: DeviceBuffer, omega: np.ndarray, log_n: int, *, in_shift=None,
+            out_shift=None, scale=None) -> None:
+    """In-place NTT of HBM-resident data (ecg_fft_dev); with in_shift / out_shift /
+    scale the shifted transform of SingleFftKernel.radix_fft_ex (ecg_fft_dev_ex)."""
     fid = _fft_field(field)
     om = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
-    _check(lib().ecg_fft_dev(prog.handle, fid, d_data.ptr, _ptr(om), log_n, None), "fft_dev")
+    if in_shift is None and out_shift is None and scale is None:
+        _check(lib().ecg_fft_dev(prog.handle, fid, d_data.ptr, _ptr(om), log_n, None), "fft_dev")
+        return
+    ps = [_fr_arg(x) for x in (in_shift, out_shift, scale)]
+    _check(lib().ecg_fft_dev_ex(prog.handle, fid, d_data.ptr, _ptr(om), log_n, *[_fr_ptr(x) for x in ps], None),
+           "fft_dev")
 
 
 def gen_bases_dev(prog: Program, curve, a: int, b: int, n: int) -> DeviceBuffer:
@@ -644,6 +656,48 @@ def _fft_field(f) -> int:
     return fid
 
 
+# scalar-field moduli: the inverses radix_ifft / coset_ifft hand to the engine
+FR_MODULUS = {
+    FIELD_BLS12_381_FR: 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001,
+    FIELD_BN254_FR: 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001,
+}
+
+
+def _fr_arg(x):
+    """An Fr element (Montgomery, 4 x u64) as a contiguous array, or None."""
+    return None if x is None else np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+
+
+def _fr_ptr(x):
+    return None if x is None else _ptr(x)
+
+
+def _mont_int(a: np.ndarray) -> int:
+    return sum(int(w) << (64 * i) for i, w in enumerate(np.asarray(a, dtype=np.uint64).reshape(4)))
+
+
+def _mont_arr(v: int) -> np.ndarray:
+    return np.array([(v >> (64 * i)) & (2**64 - 1) for i in range(4)], dtype=np.uint64)
+
+
+def fr_mont_inverse(field, a: np.ndarray) -> np.ndarray:
+    """1/a for an Fr element in Montgomery form (a R -> a^-1 R), by Python integers."""
+    r = FR_MODULUS[_fft_field(field)]
+    return _mont_arr(pow(_mont_int(a), -1, r) * pow(2, 512, r) % r)
+
+
+def fr_mont_from_int(field, v: int) -> np.ndarray:
+    r = FR_MODULUS[_fft_field(field)]
+    return _mont_arr((v << 256) % r)
+
+
+def fft_set_fused(on: bool) -> None:
+    """Shifts and scale of radix_fft_ex fused into the NTT passes (default) or
+    applied by a scaling kernel around the plain transform, process-wide
+    (ecg_fft_set_fused).  Results never depend on it."""
+    _check(lib().ecg_fft_set_fused(int(bool(on))), "fft_set_fused")
+
+
 class SingleFftKernel:
     def __init__(self, prog: Program, fid: int, maybe_abort=None):
         self.program = prog
@@ -660,6 +714,36 @@ class SingleFftKernel:
             rc = lib().ecg_fft(self.program.handle, self.fid, _ptr(inp), _ptr(om), log_n, cb, None)
         del keep
         _check(rc, "radix_fft")
+
+    def radix_fft_ex(self, inp: np.ndarray, omega: np.ndarray, log_n: int, *, in_shift=None, out_shift=None,
+                     scale=None) -> None:
+        """In place: inp[k] <- scale * out_shift^k * sum_j in_shift^j inp[j] omega^(jk)
+        (ecg_fft_ex).  The parameters are Montgomery Fr elements (4 x u64),
+        None = 1; all None is radix_fft."""
+        if inp.shape != (1 << log_n, 4):
+            raise EcError(f"radix_fft_ex: expected shape {(1 << log_n, 4)}, got {inp.shape}")
+        om = np.ascontiguousarray(omega, dtype=np.uint64).reshape(4)
+        ps = [_fr_arg(x) for x in (in_shift, out_shift, scale)]
+        cb, keep = _abort_cb(self.maybe_abort)
+        with self.program._lock:
+            rc = lib().ecg_fft_ex(self.program.handle, self.fid, _ptr(inp), _ptr(om), log_n,
+                                  *[_fr_ptr(x) for x in ps], cb, None)
+        del keep
+        _check(rc, "radix_fft_ex")
+
+    def radix_ifft(self, inp: np.ndarray, omega: np.ndarray, log_n: int) -> None:
+        """Inverse of radix_fft(omega), 1/n included."""
+        self.radix_fft_ex(inp, fr_mont_inverse(self.fid, omega), log_n,
+                          scale=fr_mont_inverse(self.fid, fr_mont_from_int(self.fid, 1 << log_n)))
+
+    def coset_fft(self, inp: np.ndarray, omega: np.ndarray, log_n: int, g: np.ndarray) -> None:
+        """Evaluations on the coset g H: inp[k] <- sum_j inp[j] (g omega^k)^j."""
+        self.radix_fft_ex(inp, omega, log_n, in_shift=g)
+
+    def coset_ifft(self, inp: np.ndarray, omega: np.ndarray, log_n: int, g: np.ndarray) -> None:
+        """Inverse of coset_fft(omega, g)."""
+        self.radix_fft_ex(inp, fr_mont_inverse(self.fid, omega), log_n, out_shift=fr_mont_inverse(self.fid, g),
+                          scale=fr_mont_inverse(self.fid, fr_mont_from_int(self.fid, 1 << log_n)))
 
 
 class FftKernel:
@@ -687,6 +771,20 @@ class FftKernel:
     def radix_fft(self, inp: np.ndarray, omega: np.ndarray, log_n: int) -> None:
         """Uses the first GPU (fft.rs:200-204)."""
         self.kernels[0].radix_fft(inp, omega, log_n)
+
+    def radix_fft_ex(self, inp: np.ndarray, omega: np.ndarray, log_n: int, *, in_shift=None, out_shift=None,
+                     scale=None) -> None:
+        """Shifted / scaled transform on the first GPU (SingleFftKernel.radix_fft_ex)."""
+        self.kernels[0].radix_fft_ex(inp, omega, log_n, in_shift=in_shift, out_shift=out_shift, scale=scale)
+
+    def radix_ifft(self, inp: np.ndarray, omega: np.ndarray, log_n: int) -> None:
+        self.kernels[0].radix_ifft(inp, omega, log_n)
+
+    def coset_fft(self, inp: np.ndarray, omega: np.ndarray, log_n: int, g: np.ndarray) -> None:
+        self.kernels[0].coset_fft(inp, omega, log_n, g)
+
+    def coset_ifft(self, inp: np.ndarray, omega: np.ndarray, log_n: int, g: np.ndarray) -> None:
+        self.kernels[0].coset_ifft(inp, omega, log_n, g)
 
     def radix_fft_many(self, inputs: Sequence[np.ndarray], omegas: Sequence[np.ndarray],
                        log_ns: Sequence[int]) -> None:

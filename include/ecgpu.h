@@ -164,6 +164,31 @@ int ecg_fft_many(ecg_ctx **ctxs, int nctx, int field_id, uint64_t **inouts, cons
 int ecg_fft_dev(ecg_ctx *ctx, int field_id, void *d_inout, const uint64_t *omega, uint32_t log_n,
                 void *stream);
 
+/* Shifted / scaled transform, in place, natural order in and out:
+ *   y[k] = scale * out_shift^k * sum_j in_shift^j * a[j] * omega^(j k),  k < 2^log_n.
+ * in_shift, out_shift and scale are Fr elements (Montgomery, 4 x u64); NULL
+ * means 1, and with all three NULL the call is ecg_fft / ecg_fft_dev (same
+ * path, same bytes).  The engine never inverts -- the caller passes omega^-1,
+ * n^-1 and g^-1 the way it passes omega:
+ *   coset FFT (evaluate on g H):   in_shift = g
+ *   inverse FFT:                   omega^-1, scale = n^-1
+ *   inverse coset FFT:             omega^-1, out_shift = g^-1, scale = n^-1
+ * (ark-poly's EvaluationDomain::{coset_fft, ifft, coset_ifft}).  The factors
+ * are folded into the NTT passes' twiddle tables (log_n <= 28: at most one
+ * extra product per element and side, none for scale alone); the table sets
+ * of the three most recent (omega, in_shift, out_shift, scale, log_n) are kept
+ * in the context next to the plain transform's, about 2^log_n x 72 B each.
+ * A zero shift or any parameter >= r is ECG_ERR_INVALID. */
+int ecg_fft_ex(ecg_ctx *ctx, int field_id, uint64_t *inout, const uint64_t *omega, uint32_t log_n,
+               const uint64_t *in_shift, const uint64_t *out_shift, const uint64_t *scale,
+               ecg_abort_cb abort_cb, void *user);
+int ecg_fft_dev_ex(ecg_ctx *ctx, int field_id, void *d_inout, const uint64_t *omega, uint32_t log_n,
+                   const uint64_t *in_shift, const uint64_t *out_shift, const uint64_t *scale, void *stream);
+/* 1 (default): shifts and scale fused into the passes; 0: a scaling kernel
+ * before / after the plain transform (what sizes above 2^28 always use).
+ * Process-wide.  Results never depend on it.  A/B and test knob. */
+int ecg_fft_set_fused(int on);
+
 /* ---- EC-FFT (FFT over G1, "FFTg") -------------------------------------------
  * In-place DFT of 2^log_n G1 points: P_k <- sum_j omega^(j k) * P_j, natural
  * order in and out, omega an Fr element (Montgomery, 4 x u64) that is a

@@ -44,6 +44,25 @@ impl<'a, F: Field + GpuName> SingleFftKernel<'a, F> {
                          omega as *const F as *const u64, log_n, cb, user)
         })
     }
+
+    /// `input` is replaced by scale * out_shift^k * sum_j in_shift^j a[j] omega^(jk);
+    /// `None` is 1.  Coset FFT: `in_shift = g`; inverse: `omega^-1`, `scale =
+    /// n^-1`; inverse coset: `omega^-1`, `out_shift = g^-1`, `scale = n^-1`.
+    pub fn radix_fft_ex(
+        &mut self, input: &mut [F], omega: &F, log_n: u32, in_shift: Option<&F>, out_shift: Option<&F>,
+        scale: Option<&F>,
+    ) -> EcResult<()> {
+        assert_eq!(input.len(), 1usize << log_n, "input length must be 2^log_n");
+        let field = field_id::<F>()?;
+        require(&self.program, sys::ECG_KIND_FFT, field)?;
+        let (cb, user) = abort_hook(&self.maybe_abort);
+        let ptr = |x: Option<&F>| x.map_or(std::ptr::null(), |v| v as *const F as *const u64);
+        check(unsafe {
+            sys::ecg_fft_ex(self.program.ctx(), field, input.as_mut_ptr() as *mut u64,
+                            omega as *const F as *const u64, log_n, ptr(in_shift), ptr(out_shift), ptr(scale),
+                            cb, user)
+        })
+    }
 }
 
 /// One FFT kernel per device.

@@ -115,6 +115,14 @@ extern "C" {
                         user: *mut c_void) -> c_int;
     pub fn ecg_fft_dev(ctx: *mut ecg_ctx, field_id: c_int, d_inout: *mut c_void, omega: *const u64,
                        log_n: u32, stream: *mut c_void) -> c_int;
+    // shifted / scaled transform: null in_shift / out_shift / scale = 1
+    pub fn ecg_fft_ex(ctx: *mut ecg_ctx, field_id: c_int, inout: *mut u64, omega: *const u64, log_n: u32,
+                      in_shift: *const u64, out_shift: *const u64, scale: *const u64,
+                      abort_cb: ecg_abort_cb, user: *mut c_void) -> c_int;
+    pub fn ecg_fft_dev_ex(ctx: *mut ecg_ctx, field_id: c_int, d_inout: *mut c_void, omega: *const u64,
+                          log_n: u32, in_shift: *const u64, out_shift: *const u64, scale: *const u64,
+                          stream: *mut c_void) -> c_int;
+    pub fn ecg_fft_set_fused(on: c_int) -> c_int;
 
     // ---- EC-FFT (ec_fft.rs:56-164, 224-270) ----
     pub fn ecg_ec_fft(ctx: *mut ecg_ctx, curve_id: c_int, inout_jac: *mut u64, omega: *const u64, log_n: u32,
