@@ -2,8 +2,9 @@
 // MSM bucket pipeline: the same formulas as curve.hpp (madd-2008-s,
 // add-2008-s, dbl-2008-s-1 / mdbl-2008-s-1; ec.cl:17-130's role), with every
 // subtraction's multiple of p chosen from a value bound, so no value ever
-// needs a conditional reduction.  Bounds, in units of p (product outputs
-// M < 1.01 p given the >= 2^25 slack):
+// needs a conditional reduction.  Bounds, in units of p, on the wide-slack
+// layouts (BLS12-381 Fq 14 x 29, BN254 Fq 10 x 28: R'/p >= 2^25, product
+// outputs M < 1.01 p; the MSM's own G1 layouts are the tight ones below):
 //   stored points  X <= 17.01, Y <= 4.01, ZZ, ZZZ <= M;  bases x, y <= M,
 //                  a negated base y is 4p - y (<= 4p, "wide" limbs)
 //   madd:  P = U2 - X1 + 64p <= 65, R = S2 - Y1 + 16p <= 17,

@@ -21,9 +21,15 @@
 //     output is the unique radix-2^BITS digit string of its value;
 //   * rr_add: exact sum, QN;  rr_sub<k>: a - b + k p, QN, for b <= k p / 2;
 //   * congruence to 0 of a product output v (< 2p) is  v == 0 || v == p.
-// The MSM formulas (curve_rr.hpp) keep every value below 64 p, far inside
-// the 2^25 (BLS12-381 Fq) / 2^26 (BN254 Fq) slack.  Outputs are converted back
-// and fully reduced, so results stay bit-identical to the reference's.
+// The slack R'/p is 2^SLACK_LOG2: 2^25 / 2^26 on the wide layouts (BLS12-381 Fq
+// 14 x 29, BN254 Fq 10 x 28: the G2 path), where the MSM formulas keep every
+// value below 64 p, and 2^6 .. 2^9 on the tight ones (Fr 9 x 29, BN254 Fq 9 x
+// 29, BLS12-381 Fq 13 x 30), whose callers bring values back to ~p with
+// rr_reduce_q (curve_rr.hpp rr_tight, ntt_pass.hpp).  Outputs are converted
+// back and fully reduced, so results stay bit-identical to the reference's.
+// tests/test_rr_contracts.py replays every clause above on exact integers at
+// its worst-case operands; tests/test_gpu_rr_ops.py runs the same operands
+// through these functions on the device (ecg_rr_ops).
 #pragma once
 #include "field.hpp"
 
@@ -90,10 +96,47 @@ ECG_DEV void mad64s(uint64_t& acc, uint32_t a, uint32_t b_uniform) {
 // (column 0 starts at -1): ceil(x / 2^B) = (z >> B) + 1 with an arithmetic
 // shift, m = ~z mod 2^B, and the +1 of one column cancels the -1 of the next,
 // so only the last reduction column adds it back.  9 mads fewer per Fr
-// product; columns stay below 2^63 in magnitude, so z never wraps.
+// product.  z is read as a SIGNED 64-bit integer (it is -1 when x = 0), so the
+// ceil form needs every column below 2^63 -- half of what the general form's
+// unsigned accumulator holds.  QN operands stay far below that; the NTT's
+// un-carried butterfly operands (limbs up to 2^31.4) do not, so a product
+// names the bound of its first operand's limbs (AMAX) and rr_ceil_fits picks
+// the form.
 template <class Q>
 constexpr bool rr_ceil_carry() {
   return Q::P[0] == 1;
+}
+// Largest limb below the top one of a QN operand: 2^BITS - 1 plus one carry.
+template <class Q>
+constexpr uint32_t rr_qn_max() {
+  return (1u << Q::BITS) + (1u << (32 - Q::BITS)) - 1;
+}
+// Bound of column k of a product a b + m p: limbs of a below the top one <=
+// amax, b QN, both top limbs <= 64 (P_top + 1) (values < 64 p), the m p terms
+// and a 2^37 carry-in.
+template <class Q>
+constexpr unsigned __int128 rr_col_bound(int k, uint32_t amax) {
+  using u128 = unsigned __int128;
+  constexpr int NL = Q::NL;
+  const u128 top = (u128)64 * ((u128)Q::P[NL - 1] + 1), qn = rr_qn_max<Q>();
+  u128 s = (u128)1 << 37;
+  const int j0 = k < NL ? 0 : k - NL + 1, j1 = k < NL ? k : NL - 1;
+  for (int i = j0; i <= j1; i++) {
+    s += (i == NL - 1 ? top : (u128)amax) * (k - i == NL - 1 ? top : qn);
+    s += (u128)((1u << Q::BITS) - 1) * (u128)Q::P[k - i];
+  }
+  return s;
+}
+// every column of such a product below 2^lg
+template <class Q>
+constexpr bool rr_cols_below(uint32_t amax, int lg) {
+  for (int k = 0; k < 2 * Q::NL - 1; k++)
+    if (rr_col_bound<Q>(k, amax) >= ((unsigned __int128)1 << lg)) return false;
+  return true;
+}
+template <class Q>
+constexpr bool rr_ceil_fits(uint32_t amax) {
+  return rr_cols_below<Q>(amax, 63);
 }
 template <class Q>
 ECG_DEV void rr_ceil_step(uint64_t& z, uint32_t& m, bool last) {
@@ -146,14 +189,23 @@ ECG_DEV void rr_join(uint64_t& x, uint64_t h) {
 }
 
 // Montgomery product (a b + m p) / R', product scanning, one v_mad_u64_u32
-// per product.
-template <class Q>
+// per product.  AMAX = 0: a and b QN.  AMAX > 0: the limbs of a below its top
+// one are <= AMAX (un-carried sums of the NTT, BITS <= 29) and b is QN; the
+// ceil form serves it only where its signed chains hold the columns.
+template <class Q, uint32_t AMAX>
+constexpr bool rr_use_ceil() {
+  static_assert(AMAX == 0 || Q::BITS <= 29, "wide operands: no column splits");
+  static_assert(AMAX == 0 || rr_cols_below<Q>(AMAX, 64), "a column would overflow the 64-bit accumulator");
+  return rr_ceil_carry<Q>() && rr_ceil_fits<Q>(AMAX ? AMAX : rr_qn_max<Q>());
+}
+template <uint32_t AMAX = 0, class Q>
 ECG_DEV FpR<Q> rr_mul(const FpR<Q>& a, const FpR<Q>& b) {
   constexpr int NL = Q::NL, B = Q::BITS;
   constexpr uint32_t MASK = (1u << B) - 1;
+  constexpr bool CEIL = rr_use_ceil<Q, AMAX>();
   uint32_t m[NL];
   FpR<Q> r;
-  uint64_t acc = rr_ceil_carry<Q>() ? ~0ull : 0ull;
+  uint64_t acc = CEIL ? ~0ull : 0ull;
 #pragma unroll
   for (int k = 0; k < NL; k++) {
 #pragma unroll
@@ -162,7 +214,7 @@ ECG_DEV FpR<Q> rr_mul(const FpR<Q>& a, const FpR<Q>& b) {
     if (rr_col_split<Q>(k)) rr_split<Q>(acc, h);
 #pragma unroll
     for (int i = 0; i < k; i++) mad64s(acc, m[i], Q::P[k - i]);
-    if constexpr (rr_ceil_carry<Q>()) {
+    if constexpr (CEIL) {
       rr_ceil_step<Q>(acc, m[k], k == NL - 1);
     } else {
       m[k] = ((uint32_t)acc * Q::INV) & MASK;
@@ -385,15 +437,16 @@ ECG_DEV void col2p(int k, int lo, int hi, uint64_t& x0, const uint32_t* m0, uint
   }
 }
 
-// r0 = a0 b0 / R', r1 = a1 b1 / R'
-template <class Q>
+// r0 = a0 b0 / R', r1 = a1 b1 / R'  (AMAX bounds the limbs of a0 and a1, see rr_mul)
+template <uint32_t AMAX = 0, class Q>
 ECG_DEV void rr_mul2(const FpR<Q>& a0, const FpR<Q>& b0, const FpR<Q>& a1, const FpR<Q>& b1, FpR<Q>& r0,
                      FpR<Q>& r1) {
   constexpr int NL = Q::NL, B = Q::BITS;
   constexpr uint32_t MASK = (1u << B) - 1;
+  constexpr bool CEIL = rr_use_ceil<Q, AMAX>();
   uint32_t m0[NL], m1[NL];
   uint64_t x0, x1;
-  if constexpr (rr_ceil_carry<Q>())
+  if constexpr (CEIL)
     mad64x2_m1(x0, a0.v[0], b0.v[0], x1, a1.v[0], b1.v[0]);  // column 0 starts both chains at -1
   else
     mad64x2_z<true, true>(x0, a0.v[0], b0.v[0], x1, a1.v[0], b1.v[0]);  // column 0 starts both chains
@@ -406,7 +459,7 @@ ECG_DEV void rr_mul2(const FpR<Q>& a0, const FpR<Q>& b0, const FpR<Q>& a1, const
       rr_split<Q>(x1, h1);
     }
     col2p<Q>(k, 0, k - 1, x0, m0, x1, m1);
-    if constexpr (rr_ceil_carry<Q>()) {
+    if constexpr (CEIL) {
       rr_ceil_step<Q>(x0, m0[k], k == NL - 1);
       rr_ceil_step<Q>(x1, m1[k], k == NL - 1);
     } else {
@@ -793,6 +846,33 @@ ECG_DEV FpR<Q> rr_sub_nc(const FpR<Q>& a, const FpR<Q>& b) {
   for (int i = 0; i < Q::NL; i++) r.v[i] = a.v[i] + Q::KP[j][i] - b.v[i];
   return r;
 }
+
+// Limb bounds (limbs below the top one) of the NTT's butterfly operands
+// (ntt_pass.hpp), from the K p rows themselves.  E: exact limbs (canonical
+// input, product outputs, rr_reduce_q, rr_carry_seq).
+template <int K, class Q>
+constexpr uint32_t rr_kp_max() {  // largest limb below the top one of the K p row
+  uint32_t m = 0;
+  for (int i = 0; i < Q::NL - 1; i++) m = Q::KP[kp_index<K>()][i] > m ? Q::KP[kp_index<K>()][i] : m;
+  return m;
+}
+template <class Q>
+struct NttLimbs {
+  static constexpr uint32_t E = (1u << Q::BITS) - 1;
+  static constexpr uint32_t D = E + rr_kp_max<8, Q>();       // e0 + 8p - e2
+  static constexpr uint32_t S = 2 * E;                       // e0 + e2; d0 + d1
+  static constexpr uint32_t A0 = 2 * S;                      // s0 + s1
+  static constexpr uint32_t A1 = S + rr_kp_max<16, Q>();     // s0 + 16p - s1
+  static constexpr uint32_t B1 = E + rr_kp_max<4, Q>();      // d0 + 4p - d1
+  static constexpr uint32_t MUL = A1 > D ? A1 : D;           // operands of the step's products (A1 > B1)
+  static constexpr uint32_t PF = A1 > A0 ? A1 : A0;          // P-form: any output of a pass's last step
+  static_assert(A1 >= B1 && PF >= D, "PF bounds every un-carried butterfly operand");
+  // rr_sub_nc stays limb-wise non-negative for subtrahend limbs <= 2^(BITS+1) - 2
+  static_assert(S <= (2u << Q::BITS) - 2, "s1 under the 16p row");
+  // rr_reduce_q: (limb + carry - q P_i) in int64 and limbs < 2^31.4; the
+  // products take PF in the unsigned general form when the ceil form cannot
+  static_assert(PF < 2833000000u, "P-form limbs stay below 2^31.4 (2.8336e9)");
+};
 
 // Exact limbs (< 2^BITS below the top limb), same value: sequential carry.
 template <class Q>

@@ -41,7 +41,14 @@ constexpr int NTT_EPT = 4;
 //
 // Values between butterfly rounds ("E-form"): exact limbs, value <= 2.5 r.
 // A radix-2^2 step on e0..e3 (r / R' <= 2^-6.1; products take one operand
-// with limbs < 2^31.6 against an exact twiddle and return < r (1 + K 2^-6.1)):
+// with un-carried limbs -- NttLimbs<Q> (fieldrr.hpp) derives their bounds from
+// the K p rows: up to 2 (2^29 - 1) + max(16p row) = 2.5 x 2^30 = 2^31.33 --
+// against an exact twiddle and return < r (1 + K 2^-6.1)).  Eight such limbs
+// against a twiddle's eight limbs of up to 2^29 - 1 put 1.20 x 2^63 into
+// column 7 (s0 + 16r - s1; 1.16 x 2^63 for s0 + s1), which BLS12-381's signed
+// ceil-carry chains misread, so every product of an un-carried operand names
+// its limb bound (rr_mul2<NttLimbs<Q>::PF>) and runs in the unsigned general
+// column form (tests/test_rr_contracts.py replays each call site):
 //   s0 = e0 + e2, d0 = (e0 + 8r - e2) w0        (<= 5 r,  <= 1.15 r)
 //   s1 = e1 + e3, d1 = (e1 + 8r - e3) w1
 //   a0 = reduce_q(s0 + s1)                      (<= 1.1 r)
@@ -50,10 +57,11 @@ constexpr int NTT_EPT = 4;
 //   b1 = (d0 + 4r - d1) w2                      (<= 1.1 r)
 // The last step of a pass (h = 1: three of its four twiddles are 1, or the
 // radix-2 round of an odd DEG) leaves its outputs unreduced ("P-form": limbs
-// < 2^31.4, value <= 21 r): they meet a product next -- the following pass
-// multiplies every element by its twiddle first, and a product of such an
-// operand with an exact twiddle is < r (1 + 21 * 2^-6.1) < 1.4 r with exact
-// limbs (column sums < 9 2^60.4 + 9 2^58 < 2^64) -- or rr_store_std's
+// <= NttLimbs<Q>::PF < 2^31.4, value <= 21 r): they meet a product next -- the
+// following pass multiplies every element by its twiddle first, and a product
+// of such an operand with an exact twiddle is < r (1 + 21 * 2^-6.1) < 1.4 r
+// with exact limbs (column sums < 9 2^60.4 + 9 2^58 < 2^64, unsigned: the
+// general column form, see above) -- or rr_store_std's
 // reduce_q (limbs < 2^31.4, value < 64 r).  The first pass reads canonical
 // input and has no twiddle product, so P-form values never enter a sum.
 //
@@ -155,6 +163,9 @@ __global__ void __launch_bounds__(NTT_RR_THREADS) __attribute__((amdgpu_waves_pe
   static_assert(!(MUL_IN && IN_RR) && !(MUL_OUT && OUT_RR), "the shift products sit at the transform's boundary");
   using F = FpR<Q>;
   constexpr uint32_t R = 1u << DEG;
+  // limb bounds of the products' first operands: the P-form (and, below it,
+  // every un-carried butterfly difference); a first pass loads canonical limbs
+  constexpr uint32_t PF = NttLimbs<Q>::PF, AIN = IN_RR ? PF : 0;
   extern __shared__ uint4 smem[];
   const uint32_t E = R << log_g;
   const RrPlanes<Q> U = RrPlanes<Q>::over(smem, E);
@@ -205,7 +216,7 @@ __global__ void __launch_bounds__(NTT_RR_THREADS) __attribute__((amdgpu_waves_pe
 #pragma unroll
       for (int q = 0; q + 1 < NTT_EPT; q += 2) {
         F p0, p1;
-        rr_mul2(v[q], w[q], v[q + 1], w[q + 1], p0, p1);
+        rr_mul2<AIN>(v[q], w[q], v[q + 1], w[q + 1], p0, p1);
         v[q] = p0;
         v[q + 1] = p1;
       }
@@ -236,24 +247,24 @@ __global__ void __launch_bounds__(NTT_RR_THREADS) __attribute__((amdgpu_waves_pe
       F a0, a1, b0, b1;
       if (h > 1) {
         F d0, d1, a1p, b1p;
-        rr_mul2(rr_sub_nc<8>(e0, e2), PQ.get((size_t)(qm << r) << pq_shift), rr_sub_nc<8>(e1, e3),
+        rr_mul2<PF>(rr_sub_nc<8>(e0, e2), PQ.get((size_t)(qm << r) << pq_shift), rr_sub_nc<8>(e1, e3),
                 PQ.get((size_t)((qm + h) << r) << pq_shift), d0, d1);
         a0 = rr_reduce_q(rr_add_nc(s0, s1));
         b0 = rr_carry_seq(rr_add_nc(d0, d1));
         const F w2 = PQ.get((size_t)(qm << (r + 1)) << pq_shift);
-        rr_mul2(rr_sub_nc<16>(s0, s1), w2, rr_sub_nc<4>(d0, d1), w2, a1p, b1p);
+        rr_mul2<PF>(rr_sub_nc<16>(s0, s1), w2, rr_sub_nc<4>(d0, d1), w2, a1p, b1p);
         a1 = a1p;
         b1 = b1p;
       } else {  // h = 1 (the pass's last step): qm = 0, only d1's twiddle w^(1 << r) is non-trivial
         const F d0 = rr_reduce_q(rr_sub_nc<8>(e0, e2));
-        const F d1 = rr_mul(rr_sub_nc<8>(e1, e3), PQ.get((size_t)(1u << r) << pq_shift));
+        const F d1 = rr_mul<PF>(rr_sub_nc<8>(e1, e3), PQ.get((size_t)(1u << r) << pq_shift));
         // Left unreduced ("P-form", see the header): every consumer -- the
         // next pass's twiddle product or rr_store_std's reduce_q -- takes
         // limbs < 2^31.4 and values < 64 r.
-        a0 = rr_add_nc(s0, s1);      // <= 10 r, limbs < 2^31
-        a1 = rr_sub_nc<16>(s0, s1);  // <= 21 r, limbs < 2^30 + 2^30.6
-        b0 = rr_add_nc(d0, d1);      // <= 2.3 r
-        b1 = rr_sub_nc<4>(d0, d1);   // <= 5.2 r, limbs < 2^29 + 2^30.6
+        a0 = rr_add_nc(s0, s1);      // <= 10 r, limbs <= NttLimbs::A0 = 2^31 - 4
+        a1 = rr_sub_nc<16>(s0, s1);  // <= 21 r, limbs <= NttLimbs::A1 = 2^30 - 2 + max(16p row) < 2.5 x 2^30
+        b0 = rr_add_nc(d0, d1);      // <= 2.3 r, limbs <= NttLimbs::S
+        b1 = rr_sub_nc<4>(d0, d1);   // <= 5.2 r, limbs <= NttLimbs::B1 = 2^29 - 1 + max(4p row) < 2^31
       }
       U.put(pj, a0);
       U.put(pj ^ oh, a1);
@@ -267,7 +278,7 @@ __global__ void __launch_bounds__(NTT_RR_THREADS) __attribute__((amdgpu_waves_pe
       const uint32_t p0 = lds_phys(2 * f);  // phys(2f + 1) = phys(2f) ^ 1
       const F u0 = U.get(p0), u1 = U.get(p0 ^ 1);
       U.put(p0, rr_add_nc(u0, u1));           // <= 5 r
-      U.put(p0 ^ 1, rr_sub_nc<8>(u0, u1));    // <= 10.5 r, limbs < 2^29 + 2^30.6
+      U.put(p0 ^ 1, rr_sub_nc<8>(u0, u1));    // <= 10.5 r, limbs <= NttLimbs::D < 2^31
     }
     __syncthreads();
   }
@@ -311,7 +322,7 @@ __global__ void __launch_bounds__(NTT_RR_THREADS) __attribute__((amdgpu_waves_pe
 #pragma unroll
       for (int q = 0; q + 1 < NTT_EPT; q += 2) {
         F p0, p1;
-        rr_mul2(v[q], w[q], v[q + 1], w[q + 1], p0, p1);
+        rr_mul2<PF>(v[q], w[q], v[q + 1], w[q + 1], p0, p1);
         v[q] = p0;
         v[q + 1] = p1;
       }

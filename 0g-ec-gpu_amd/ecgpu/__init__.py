@@ -47,6 +47,7 @@ ECG_OK, ECG_ABORTED = 0, 1
 ECG_ERR_INVALID, ECG_ERR_HIP, ECG_ERR_NOMEM, ECG_ERR_NODEV, ECG_ERR_RCCL = -1, -2, -3, -4, -5
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 ABORT_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
 # ecg_xchg_cb(op, send, recv, bytes, user): the host transport of ecg_comm_init_host
 XCHG_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -104,6 +105,8 @@ _SIGS = {
     "ecg_point_sum": (ctypes.c_int, [ctypes.c_int, _u64p, ctypes.c_size_t, _u64p]),
     "ecg_field_ops": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _u64p, _u64p,
                                      ctypes.c_uint32, ctypes.c_size_t, _u64p]),
+    "ecg_rr_ops": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _u32p, _u32p, _u32p, _u32p,
+                                  ctypes.c_size_t, _u32p, _u32p, _u32p]),
     "ecg_ec_fft": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, ctypes.c_uint32, ABORT_CB,
                                   ctypes.c_void_p]),
     "ecg_ec_fft_many": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
@@ -468,6 +471,30 @@ def field_ops(prog: Program, field, form: int, op: int, a: np.ndarray, b: np.nda
     _check(lib().ecg_field_ops(prog.handle, fid, form, op, _ptr(a), _ptr(bb) if bb is not None else None, int(e),
                                a.shape[0], _ptr(out)), "field_ops")
     return out
+
+
+# ecg_rr_ops: the reduced-radix limb layouts (name -> id, NL, BITS) and ops
+RR_LAYOUTS = {"bls12_381_fr": (0, 9, 29), "bn254_fr": (1, 9, 29), "bls12_381_fq13": (2, 13, 30),
+              "bls12_381_fq": (3, 14, 29), "bn254_fq9": (4, 9, 29), "bn254_fq": (5, 10, 28)}
+(RROP_MUL, RROP_MUL2, RROP_SQR, RROP_SQR2, RROP_MUL_SUM2, RROP_ADD,
+ RROP_SUB, RROP_NEG, RROP_SUB2, RROP_SUB3, RROP_NEG_WIDE, RROP_ADD_NC,
+ RROP_SUB_NC, RROP_CARRY, RROP_CARRY_SEQ, RROP_REDUCE_Q, RROP_CANON_LT2P, RROP_FROM_STD,
+ RROP_TO_STD, RROP_IS_ZERO_PROD, RROP_MAYBE_ZERO_PROD, RROP_MUL_NTT, RROP_MUL2_NTT) = range(23)
+
+
+def rr_ops(prog: Program, layout, op: int, *operands: np.ndarray, k: int = 0):
+    """ecg_rr_ops: one fieldrr.hpp primitive element-wise on raw limbs, used
+    as given (no rr_from_std).  operands: up to four (n, NL) uint32 arrays.
+    Returns (out0, out1, flags): two (n, NL) uint32 arrays and n uint32."""
+    lid = RR_LAYOUTS[layout][0] if isinstance(layout, str) else int(layout)
+    ops_ = [np.ascontiguousarray(x, dtype=np.uint32) for x in operands]
+    n = ops_[0].shape[0]
+    out0, out1 = np.zeros_like(ops_[0]), np.zeros_like(ops_[0])
+    flags = np.zeros(n, dtype=np.uint32)
+    p32 = lambda x: x.ctypes.data_as(_u32p)
+    args = [p32(x) for x in ops_] + [None] * (4 - len(ops_))
+    _check(lib().ecg_rr_ops(prog.handle, lid, int(op), int(k), *args, n, p32(out0), p32(out1), p32(flags)), "rr_ops")
+    return out0, out1, flags
 
 
 def msm_grid_part(prog: Program, curve, d_bases: DeviceBuffer, d_scalars: DeviceBuffer, n: int, rank: int,

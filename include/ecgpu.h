@@ -361,6 +361,52 @@ int ecg_msm_plan_info(int curve_id, size_t n, uint32_t window_bits, uint32_t *c,
 int ecg_field_ops(ecg_ctx *ctx, int field_id, int form, int op, const uint64_t *a, const uint64_t *b, uint32_t e,
                   size_t n, uint64_t *out);
 
+/* One reduced-radix primitive (csrc/fieldrr.hpp) element-wise on RAW limbs:
+ * no rr_from_std on the way in, so quasi-normalised limbs, lazy values of
+ * many p, wide negations and un-carried sums reach the very inline functions
+ * the MSM / NTT kernels call.  For the tests of those functions' contracts.
+ * layout: one of the six limb layouts below (NL limbs of BITS bits).  a, b,
+ * c, d, out0, out1: n rows of NL uint32 limbs, host memory; operands an op
+ * does not take may be NULL, out1 may be NULL unless op has two outputs
+ * (MUL2: a b and c d; SQR2: a^2 and b^2), flags (n words) may be NULL unless
+ * op is a predicate.  k: the multiple of p of SUB / NEG / SUB2 / SUB3 /
+ * NEG_WIDE / SUB_NC, a power of two whose row the layout holds
+ * (ECG_ERR_INVALID otherwise).  FROM_STD reads, TO_STD writes the boundary
+ * form (32-bit words, R = 2^(64N)) in the first words of a row.  MUL_NTT /
+ * MUL2_NTT: the NTT's product of an un-carried butterfly operand with an
+ * exact twiddle (the two scalar-field layouts only). */
+#define ECG_RR_BLS12_381_FR 0   /*  9 x 29 */
+#define ECG_RR_BN254_FR 1       /*  9 x 29 */
+#define ECG_RR_BLS12_381_FQ13 2 /* 13 x 30 */
+#define ECG_RR_BLS12_381_FQ14 3 /* 14 x 29 */
+#define ECG_RR_BN254_FQ9 4      /*  9 x 29 */
+#define ECG_RR_BN254_FQ10 5     /* 10 x 28 */
+#define ECG_RROP_MUL 0
+#define ECG_RROP_MUL2 1
+#define ECG_RROP_SQR 2
+#define ECG_RROP_SQR2 3
+#define ECG_RROP_MUL_SUM2 4
+#define ECG_RROP_ADD 5
+#define ECG_RROP_SUB 6
+#define ECG_RROP_NEG 7
+#define ECG_RROP_SUB2 8
+#define ECG_RROP_SUB3 9
+#define ECG_RROP_NEG_WIDE 10
+#define ECG_RROP_ADD_NC 11
+#define ECG_RROP_SUB_NC 12
+#define ECG_RROP_CARRY 13
+#define ECG_RROP_CARRY_SEQ 14
+#define ECG_RROP_REDUCE_Q 15
+#define ECG_RROP_CANON_LT2P 16
+#define ECG_RROP_FROM_STD 17
+#define ECG_RROP_TO_STD 18
+#define ECG_RROP_IS_ZERO_PROD 19
+#define ECG_RROP_MAYBE_ZERO_PROD 20
+#define ECG_RROP_MUL_NTT 21
+#define ECG_RROP_MUL2_NTT 22
+int ecg_rr_ops(ecg_ctx *ctx, int layout, int op, int k, const uint32_t *a, const uint32_t *b, const uint32_t *c,
+               const uint32_t *d, size_t n, uint32_t *out0, uint32_t *out1, uint32_t *flags);
+
 /* Sum `count` Jacobian points (3 x Lq u64 each, device memory) into one
  * normalised Jacobian point: the EC fold that follows the RCCL all-gather of
  * per-GPU partials (RCCL has no EC-add reduction op).  The points are copied

@@ -50,6 +50,36 @@ pub const ECG_FOP_POW: c_int = 5;
 pub const ECG_FOP_MONT: c_int = 6;
 pub const ECG_FOP_UNMONT: c_int = 7;
 pub const ECG_FOP_INV: c_int = 8;
+// ---- ecg_rr_ops layouts and ops ------------------------------------------------
+pub const ECG_RR_BLS12_381_FR: c_int = 0;
+pub const ECG_RR_BN254_FR: c_int = 1;
+pub const ECG_RR_BLS12_381_FQ13: c_int = 2;
+pub const ECG_RR_BLS12_381_FQ14: c_int = 3;
+pub const ECG_RR_BN254_FQ9: c_int = 4;
+pub const ECG_RR_BN254_FQ10: c_int = 5;
+pub const ECG_RROP_MUL: c_int = 0;
+pub const ECG_RROP_MUL2: c_int = 1;
+pub const ECG_RROP_SQR: c_int = 2;
+pub const ECG_RROP_SQR2: c_int = 3;
+pub const ECG_RROP_MUL_SUM2: c_int = 4;
+pub const ECG_RROP_ADD: c_int = 5;
+pub const ECG_RROP_SUB: c_int = 6;
+pub const ECG_RROP_NEG: c_int = 7;
+pub const ECG_RROP_SUB2: c_int = 8;
+pub const ECG_RROP_SUB3: c_int = 9;
+pub const ECG_RROP_NEG_WIDE: c_int = 10;
+pub const ECG_RROP_ADD_NC: c_int = 11;
+pub const ECG_RROP_SUB_NC: c_int = 12;
+pub const ECG_RROP_CARRY: c_int = 13;
+pub const ECG_RROP_CARRY_SEQ: c_int = 14;
+pub const ECG_RROP_REDUCE_Q: c_int = 15;
+pub const ECG_RROP_CANON_LT2P: c_int = 16;
+pub const ECG_RROP_FROM_STD: c_int = 17;
+pub const ECG_RROP_TO_STD: c_int = 18;
+pub const ECG_RROP_IS_ZERO_PROD: c_int = 19;
+pub const ECG_RROP_MAYBE_ZERO_PROD: c_int = 20;
+pub const ECG_RROP_MUL_NTT: c_int = 21;
+pub const ECG_RROP_MUL2_NTT: c_int = 22;
 pub const ECG_SORT_GLOBAL: c_int = 0;
 pub const ECG_SORT_PW_ONE: c_int = 1;
 pub const ECG_SORT_PW_BLOCK: c_int = 2;
@@ -167,6 +197,10 @@ extern "C" {
     pub fn ecg_point_sum(curve_id: c_int, points: *const u64, count: usize, out_jac: *mut u64) -> c_int;
     pub fn ecg_field_ops(ctx: *mut ecg_ctx, field_id: c_int, form: c_int, op: c_int, a: *const u64, b: *const u64,
                          e: u32, n: usize, out: *mut u64) -> c_int;
+    // one fieldrr.hpp primitive on raw limbs (contract tests)
+    pub fn ecg_rr_ops(ctx: *mut ecg_ctx, layout: c_int, op: c_int, k: c_int, a: *const u32, b: *const u32,
+                      c: *const u32, d: *const u32, n: usize, out0: *mut u32, out1: *mut u32,
+                      flags: *mut u32) -> c_int;
     pub fn ecg_msm_check_bases(curve_id: c_int, bases_xy: *const u64, scalars: *const u64, n: usize) -> c_int;
 
     // ---- multi-GPU over RCCL, one process per GPU ----

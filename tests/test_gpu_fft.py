@@ -109,6 +109,53 @@ def test_fft_edge_values(kernels):
         assert (a == ref).all()
 
 
+def _adversarial_inputs(f, n):
+    """Stored words (any integer < r is a valid Montgomery form; the reduced-radix
+    passes re-read it as 9 limbs of 29 bits) that drive the butterflies' limbs
+    to their extremes (tests/test_rr_contracts.py, the NTT call-site classes):
+    w = all eight low limbs at 2^29 - 1 below r; w alternating with 0 at strides
+    1, 2 and 4 both ways round (s0 = e0 + e2 maximal while s1 is zero, and the
+    reverse); all r - 1."""
+    T = 1 << 232
+    w = (f.modulus // T) * T - 1
+    assert w < f.modulus and all((w >> (29 * i)) & ((1 << 29) - 1) == (1 << 29) - 1 for i in range(8))
+    pats = {"all_w": [w] * n, "all_r-1": [f.modulus - 1] * n}
+    for st in (1, 2, 4):
+        pats[f"w0_stride{st}"] = [w if (j // st) % 2 == 0 else 0 for j in range(n)]
+        pats[f"0w_stride{st}"] = [0 if (j // st) % 2 == 0 else w for j in range(n)]
+    return pats
+
+
+@pytest.mark.parametrize("fname,fid", FIELDS)
+def test_fft_adversarial_limbs(kernels, fname, fid):
+    """Worst-case limb patterns through the smallest transforms that take every
+    path of the reduced-radix pass -- the h > 1 and h = 1 radix-4 steps, the odd
+    last round, one pass and two -- plain and with the shift products, fused
+    and unfused, bit-exact against the CPU FFT."""
+    from test_gpu_fft_ext import mode_params, mont, reference
+    f = po.FIELDS[fname]
+    k = kernels[fname]
+    try:
+        for log_n in (2, 3, 4, 5, 10, 11, 13):
+            n = 1 << log_n
+            om, s, t, c = mode_params(f, log_n, "general")
+            for pname, vals in _adversarial_inputs(f, n).items():
+                a = co.u64arr(vals, 4)
+                plain = co.serial_fft(fid, a, mont(f, om), log_n) if log_n <= 12 else \
+                    co.parallel_fft(fid, a, mont(f, om), log_n, 4)
+                shifted = reference(f, fid, a, log_n, om, s, t, c)
+                for fused in (True, False):
+                    ecgpu.fft_set_fused(fused)
+                    g = a.copy()
+                    k.radix_fft(g, mont(f, om), log_n)
+                    assert (g == plain).all(), (fname, log_n, pname, fused)
+                    g = a.copy()
+                    k.radix_fft_ex(g, mont(f, om), log_n, in_shift=mont(f, s), out_shift=mont(f, t), scale=mont(f, c))
+                    assert (g == shifted).all(), (fname, log_n, pname, fused, "shifted")
+    finally:
+        ecgpu.fft_set_fused(True)
+
+
 def test_inverse_round_trip_2p22(kernels):
     """Size-independent property at 2^22: FFT(omega^-1) o FFT(omega) = n * id."""
     f = po.BLS12_381_FR
