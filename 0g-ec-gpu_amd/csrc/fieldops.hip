@@ -17,6 +17,7 @@
 
 #include "ctx.hpp"
 #include "fieldrr.hpp"
+#include "fieldrr_inv.hpp"
 
 namespace ecg {
 
@@ -45,20 +46,6 @@ ECG_DEV FpR<Q> rr_pow_u32(FpR<Q> base, uint32_t e) {
     if (e & 1) r = rr_mul(r, base);
     e >>= 1;
     if (e) base = rr_sqr(base);
-  }
-  return r;
-}
-
-template <class Q>
-ECG_DEV FpR<Q> rr_inv_fermat(const FpR<Q>& a) {  // a^(p-2), MSB first
-  using P = typename Q::Base;
-  FpR<Q> r = FpR<Q>::one();
-  for (int i = P::N - 1; i >= 0; i--) {
-    const uint64_t e = P::PM2[i];
-    for (int bit = 63; bit >= 0; bit--) {
-      r = rr_sqr(r);
-      if ((e >> bit) & 1) r = rr_mul(r, a);
-    }
   }
   return r;
 }

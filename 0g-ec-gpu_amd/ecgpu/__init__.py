@@ -91,6 +91,11 @@ _SIGS = {
     "ecg_fft_dev_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, _u64p, ctypes.c_uint32, _u64p,
                                       _u64p, _u64p, ctypes.c_void_p]),
     "ecg_fft_set_fused": (ctypes.c_int, [ctypes.c_int]),
+    "ecg_poly_div_linear_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, _u64p,
+                                               ctypes.c_void_p, _u64p, ctypes.c_uint32, ctypes.c_void_p]),
+    "ecg_batch_inverse_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_size_t, _u64p, ctypes.c_void_p]),
+    "ecg_fr_scan_tile": (ctypes.c_size_t, []),
     "ecg_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
     "ecg_msm_multi": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, _u64p, _u64p,
                                      ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
@@ -595,6 +600,45 @@ def fft_dev(prog: Program, field, d_data: DeviceBuffer, omega: np.ndarray, log_n
     ps = [_fr_arg(x) for x in (in_shift, out_shift, scale)]
     _check(lib().ecg_fft_dev_ex(prog.handle, fid, d_data.ptr, _ptr(om), log_n, *[_fr_ptr(x) for x in ps], None),
            "fft_dev")
+
+
+POLY_OUT_CANONICAL = 1
+
+
+def _dev_ptr(d):
+    """A DeviceBuffer's pointer, or a raw device address (an offset into a buffer)."""
+    return d.ptr if isinstance(d, DeviceBuffer) else ctypes.c_void_p(int(d))
+
+
+def poly_div_linear_dev(prog: Program, field, d_coeffs, n: int, z: np.ndarray, d_out=None, *, canonical=False,
+                        want_value=True, flags=None):
+    """p(X) = q(X)(X - z) + p(z) over HBM-resident coefficients (ecg_poly_div_linear_dev):
+    d_out[0] = p(z), d_out[1:] = q; d_out may be d_coeffs (in place), None = evaluation only.
+    z: Montgomery Fr (4 x u64).  canonical: outputs leave Montgomery form (MSM scalars).
+    Returns p(z) (4 x u64, the form of d_out[0]; Montgomery when d_out is None), or None with
+    want_value=False (the call then does not synchronise)."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    zz = _fr_arg(z)
+    val = np.zeros(4, dtype=np.uint64) if want_value else None
+    fl = (POLY_OUT_CANONICAL if canonical else 0) if flags is None else int(flags)
+    _check(lib().ecg_poly_div_linear_dev(prog.handle, fid, _dev_ptr(d_coeffs), n, _fr_ptr(zz),
+                                         None if d_out is None else _dev_ptr(d_out), _fr_ptr(val), fl, None),
+           "poly_div_linear_dev")
+    return val
+
+
+def batch_inverse_dev(prog: Program, field, d_in, n: int, d_out=None, *, scale=None) -> None:
+    """d_out[i] = scale / d_in[i] over HBM-resident Montgomery Fr, zeros kept
+    (ecg_batch_inverse_dev, ark_ff::batch_inversion_and_mul); d_out=None: in place."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    sc = _fr_arg(scale)
+    _check(lib().ecg_batch_inverse_dev(prog.handle, fid, _dev_ptr(d_in), _dev_ptr(d_in if d_out is None else d_out), n,
+                                       _fr_ptr(sc), None), "batch_inverse_dev")
+
+
+def fr_scan_tile() -> int:
+    """Elements per workgroup tile of poly_div_linear_dev / batch_inverse_dev."""
+    return int(lib().ecg_fr_scan_tile())
 
 
 def gen_bases_dev(prog: Program, curve, a: int, b: int, n: int) -> DeviceBuffer:

@@ -189,6 +189,43 @@ int ecg_fft_dev_ex(ecg_ctx *ctx, int field_id, void *d_inout, const uint64_t *om
  * Process-wide.  Results never depend on it.  A/B and test knob. */
 int ecg_fft_set_fused(int on);
 
+/* ---- Fr scans on resident data --------------------------------------------
+ * The two steps a prover takes between an NTT and an MSM without leaving the
+ * device: opening a polynomial at a point and inverting a vector.  Both run on
+ * d_* device pointers on ctx's device (n x 32 B, Montgomery Fr as everywhere);
+ * `stream` is a hipStream_t (NULL = the context's stream).  field_id is
+ * ECG_FIELD_BLS12_381_FR or ECG_FIELD_BN254_FR; n is any size from 1 to 2^32,
+ * not only powers of two; n = 0 returns ECG_OK and touches nothing.  Three
+ * launches per call (tile reduce, one-workgroup scan, tile apply); the
+ * workspace, about n / 2048 x 72 B, is the context's ("fr_scan_*",
+ * ecg_ctx_release_workspace frees it).  The calls do not synchronise unless
+ * value_out is given. */
+#define ECG_POLY_OUT_CANONICAL 1  /* outputs leave Montgomery form: BigInt<4>, what ecg_msm_dev takes as scalars */
+
+/* Synthetic division of p (n coefficients, ascending, Montgomery Fr, device memory) by (X - z).
+ * d_out gets n elements: d_out[0] = p(z), d_out[1 + j] = q_j for j < n - 1, where
+ * p(X) = q(X)(X - z) + p(z).  That is d_out[j] = s_j with s_j = p_j + z s_{j+1}, s_n = 0.
+ * Replaces ark-poly's DensePolynomial::evaluate and the division by X - z of
+ * ark-poly-commit's KZG10::open (compute_witness_polynomial): the quotient's
+ * coefficients are the next MSM's scalars.
+ * d_out == d_coeffs (in place) is allowed; any other overlap is ECG_ERR_INVALID.
+ * d_out == NULL: evaluation only (the reduce phases, no third launch).
+ * value_out (host, 4 x u64, may be NULL) receives p(z) in the same form as d_out[0]
+ * (Montgomery when d_out is NULL).  z: host, Montgomery, < r.  n >= 1.
+ * Unknown flag bits and z >= r are ECG_ERR_INVALID. */
+int ecg_poly_div_linear_dev(ecg_ctx *ctx, int field_id, const void *d_coeffs, size_t n, const uint64_t *z,
+                            void *d_out, uint64_t *value_out, uint32_t flags, void *stream);
+
+/* d_out[i] = scale * d_in[i]^-1, zeros stay zero (ark_ff::batch_inversion_and_mul); scale NULL = 1.
+ * In place allowed (any other overlap is ECG_ERR_INVALID).  Montgomery in and out; scale: host,
+ * Montgomery, < r.  ONE field inversion per call (Montgomery's trick: about four products per
+ * element), where ECG_FOP_INV of ecg_field_ops runs one Fermat ladder per element. */
+int ecg_batch_inverse_dev(ecg_ctx *ctx, int field_id, const void *d_in, void *d_out, size_t n,
+                          const uint64_t *scale, void *stream);
+
+/* Elements per workgroup tile of the two calls above (tests place their sizes around its multiples). */
+size_t ecg_fr_scan_tile(void);
+
 /* ---- EC-FFT (FFT over G1, "FFTg") -------------------------------------------
  * In-place DFT of 2^log_n G1 points: P_k <- sum_j omega^(j k) * P_j, natural
  * order in and out, omega an Fr element (Montgomery, 4 x u64) that is a

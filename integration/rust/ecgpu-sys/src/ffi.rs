@@ -50,6 +50,10 @@ pub const ECG_FOP_POW: c_int = 5;
 pub const ECG_FOP_MONT: c_int = 6;
 pub const ECG_FOP_UNMONT: c_int = 7;
 pub const ECG_FOP_INV: c_int = 8;
+
+// ecg_poly_div_linear_dev flags
+pub const ECG_POLY_OUT_CANONICAL: c_int = 1;
+
 // ---- ecg_rr_ops layouts and ops ------------------------------------------------
 pub const ECG_RR_BLS12_381_FR: c_int = 0;
 pub const ECG_RR_BN254_FR: c_int = 1;
@@ -153,6 +157,14 @@ extern "C" {
                           log_n: u32, in_shift: *const u64, out_shift: *const u64, scale: *const u64,
                           stream: *mut c_void) -> c_int;
     pub fn ecg_fft_set_fused(on: c_int) -> c_int;
+
+    // ---- Fr scans on resident data: division by (X - z), batch inversion ----
+    pub fn ecg_poly_div_linear_dev(ctx: *mut ecg_ctx, field_id: c_int, d_coeffs: *const c_void, n: usize,
+                                   z: *const u64, d_out: *mut c_void, value_out: *mut u64, flags: u32,
+                                   stream: *mut c_void) -> c_int;
+    pub fn ecg_batch_inverse_dev(ctx: *mut ecg_ctx, field_id: c_int, d_in: *const c_void, d_out: *mut c_void,
+                                 n: usize, scale: *const u64, stream: *mut c_void) -> c_int;
+    pub fn ecg_fr_scan_tile() -> usize;
 
     // ---- EC-FFT (ec_fft.rs:56-164, 224-270) ----
     pub fn ecg_ec_fft(ctx: *mut ecg_ctx, curve_id: c_int, inout_jac: *mut u64, omega: *const u64, log_n: u32,
