@@ -219,6 +219,8 @@ int msm_prepare_run(ecg_ctx* ctx, int curve_id, const void* d_bases, size_t n, u
 // Release a prepared buffer (its header allocation) if p is one: true when
 // handled, false for any other pointer (the caller frees it).
 bool msm_prepared_free(void* p);
+// Forget a fixed-base table (fixed_base.hip) whose memory is being freed.
+void fb_table_forget(const void* p);
 size_t msm_prepared_stride(int curve_id, uint32_t tab_c);  // bytes per base of a prepared buffer
 // Plan of a one-task MSM of n terms (window_bits = 0: automatic): window
 // bits, windows, and how the sorted entries are grouped (ECG_SORT_* in ecgpu.h).

@@ -915,6 +915,7 @@ void ecg_dev_free(ecg_ctx* ctx, void* p) {
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  fb_table_forget(p);
   // a prepared-bases buffer (from any context) is unregistered with its memory
   if (!msm_prepared_free(p)) (void)hipFree(p);
 }

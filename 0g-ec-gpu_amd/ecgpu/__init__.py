@@ -96,6 +96,13 @@ _SIGS = {
     "ecg_batch_inverse_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_size_t, _u64p, ctypes.c_void_p]),
     "ecg_fr_scan_tile": (ctypes.c_size_t, []),
+    "ecg_fixed_base_plan_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)]),
+    "ecg_fixed_base_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, ctypes.c_uint32,
+                                            ctypes.POINTER(ctypes.c_void_p)]),
+    "ecg_fixed_base_mul_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
     "ecg_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
     "ecg_msm_multi": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, _u64p, _u64p,
                                      ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
@@ -639,6 +646,62 @@ def batch_inverse_dev(prog: Program, field, d_in, n: int, d_out=None, *, scale=N
 def fr_scan_tile() -> int:
     """Elements per workgroup tile of poly_div_linear_dev / batch_inverse_dev."""
     return int(lib().ecg_fr_scan_tile())
+
+
+FB_SCALARS_MONTGOMERY = 1
+
+
+class FixedBaseTable(DeviceBuffer):
+    """The comb table of one base (ecg_fixed_base_table): what fixed_base_mul_dev
+    gathers from.  Immutable and not readable, like PreparedBases; `window` is
+    the value it was built with (0 = the engine's choice)."""
+
+    def __init__(self, prog: Program, ptr: ctypes.c_void_p, curve_id: int, window: int, nbytes: int):
+        self.program = prog
+        self.ptr = ptr
+        self.curve_id = curve_id
+        self.window = window
+        self.nbytes = nbytes
+
+    def write(self, host: np.ndarray) -> None:
+        raise EcError("FixedBaseTable is immutable: build a new table instead")
+
+    def read(self, dtype=np.uint64, shape=None) -> np.ndarray:
+        raise EcError("FixedBaseTable holds the kernel's internal layout")
+
+
+def fixed_base_plan_info(curve, window: int = 0) -> tuple[int, int, int]:
+    """(windows W, entries per row 2^(c-1), table bytes) of a fixed-base table with
+    window c (0 = the engine's choice); ecg_fixed_base_plan_info, no device needed."""
+    w, rows, nbytes = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_size_t()
+    _check(lib().ecg_fixed_base_plan_info(_curve(curve), int(window), ctypes.byref(w), ctypes.byref(rows),
+                                          ctypes.byref(nbytes)), "fixed_base_plan_info")
+    return w.value, rows.value, nbytes.value
+
+
+def fixed_base_table(prog: Program, curve, base=None, window: int = 0) -> FixedBaseTable:
+    """The table of `base` ([x | y] Montgomery, 2*Lq u64; None = the generator) for
+    fixed_base_mul_dev (ecg_fixed_base_table; arkworks' FixedBase::get_window_table)."""
+    cid = _curve(curve)
+    b = None if base is None else np.ascontiguousarray(base, dtype=np.uint64).reshape(2 * CURVE_FQ_LIMBS[cid])
+    p = ctypes.c_void_p()
+    _check(lib().ecg_fixed_base_table(prog.handle, cid, None if b is None else _ptr(b), int(window), ctypes.byref(p)),
+           "fixed_base_table")
+    return FixedBaseTable(prog, p, cid, int(window), fixed_base_plan_info(cid, window)[2])
+
+
+def fixed_base_mul_dev(prog: Program, curve, table: FixedBaseTable, d_scalars, n: int, d_out=None, *,
+                       scalars_montgomery: bool = False) -> DeviceBuffer:
+    """out[i] = scalars[i] * B over n HBM-resident scalars (ecg_fixed_base_mul_dev;
+    arkworks' FixedBase::msm).  Returns d_out (allocated when None): n [x | y] base
+    records, the identity as zeros -- bases for msm_dev / prepare_bases."""
+    cid = _curve(curve)
+    if d_out is None:
+        d_out = DeviceBuffer(prog, n * 2 * CURVE_FQ_LIMBS[cid] * 8)
+    _check(lib().ecg_fixed_base_mul_dev(prog.handle, cid, table.ptr, table.window, _dev_ptr(d_scalars), n,
+                                        FB_SCALARS_MONTGOMERY if scalars_montgomery else 0, _dev_ptr(d_out), None),
+           "fixed_base_mul_dev")
+    return d_out
 
 
 def gen_bases_dev(prog: Program, curve, a: int, b: int, n: int) -> DeviceBuffer:

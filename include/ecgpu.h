@@ -226,6 +226,42 @@ int ecg_batch_inverse_dev(ecg_ctx *ctx, int field_id, const void *d_in, void *d_
 /* Elements per workgroup tile of the two calls above (tests place their sizes around its multiples). */
 size_t ecg_fr_scan_tile(void);
 
+/* ---- fixed-base batch scalar multiplication (G1) -----------------------------
+ * out_i = s_i * B for n device-resident scalars and ONE base B: arkworks'
+ * FixedBase::msm / batch_mul, the step that makes a structured reference
+ * string [tau^i]G, Lagrange or blinded bases, or any vector of commitments to
+ * single scalars -- the data ecg_msm_prepare_bases, ecg_msm_dev and the EC-FFT
+ * then consume without leaving the device.  curve_id is ECG_CURVE_BLS12_381 or
+ * ECG_CURVE_BN254 (G2 ids are ECG_ERR_INVALID).  A comb over signed windows of
+ * window_bits = c bits (2..16; 0 = the engine's choice): W = ceil((|r| + 1) / c)
+ * windows, a table of W rows of 2^(c-1) affine points d * 2^(c w) * B, and per
+ * scalar W mixed additions and no doubling, normalised in the same launch
+ * with one field inversion per 512 outputs. */
+#define ECG_FB_SCALARS_MONTGOMERY 1u /* d_scalars are Fr Montgomery elements (converted on the device) */
+
+/* W, the entries per row 2^(c-1) and the table's size in bytes for window_bits
+ * (0: the default's values).  Host only; output pointers may be NULL. */
+int ecg_fixed_base_plan_info(int curve_id, uint32_t window_bits, uint32_t *windows, uint32_t *row_entries,
+                             size_t *table_bytes);
+/* Builds the table of B on ctx's device and returns it in *d_table.  base_xy:
+ * one host [x, y] record (Montgomery, 2 x Lq u64); NULL = the curve's
+ * generator.  The identity, a point off the curve and a coordinate >= q are
+ * ECG_ERR_INVALID.  The table belongs to its device, is immutable and is
+ * released with ecg_dev_free -- never with hipFree.  Synchronous. */
+int ecg_fixed_base_table(ecg_ctx *ctx, int curve_id, const uint64_t *base_xy /* NULL = the generator */,
+                         uint32_t window_bits /* 0 = engine's choice */, void **d_table);
+/* d_out[i] = d_scalars[i] * B.  d_scalars: n BigInt<4> (canonical; any 256-bit
+ * word is reduced mod r), or Fr Montgomery elements with
+ * ECG_FB_SCALARS_MONTGOMERY.  d_out: n base records [x, y] (2 x Lq u64,
+ * Montgomery, fully reduced; the identity, s_i = 0, is the all-zero record):
+ * what ecg_msm_prepare_bases and ecg_msm_dev take as d_bases.  d_table must
+ * come from ecg_fixed_base_table for the same curve, and window_bits must name
+ * the table's window (0 = the default window).  n = 0 returns ECG_OK and
+ * touches nothing; n <= 2^32.  `stream` is a hipStream_t; NULL = the context's
+ * stream, and the call then waits for the result. */
+int ecg_fixed_base_mul_dev(ecg_ctx *ctx, int curve_id, const void *d_table, uint32_t window_bits,
+                           const void *d_scalars, size_t n, uint32_t flags, void *d_out, void *stream);
+
 /* ---- EC-FFT (FFT over G1, "FFTg") -------------------------------------------
  * In-place DFT of 2^log_n G1 points: P_k <- sum_j omega^(j k) * P_j, natural
  * order in and out, omega an Fr element (Montgomery, 4 x u64) that is a

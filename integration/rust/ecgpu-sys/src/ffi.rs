@@ -54,6 +54,9 @@ pub const ECG_FOP_INV: c_int = 8;
 // ecg_poly_div_linear_dev flags
 pub const ECG_POLY_OUT_CANONICAL: c_int = 1;
 
+// ecg_fixed_base_mul_dev flags
+pub const ECG_FB_SCALARS_MONTGOMERY: c_int = 1;
+
 // ---- ecg_rr_ops layouts and ops ------------------------------------------------
 pub const ECG_RR_BLS12_381_FR: c_int = 0;
 pub const ECG_RR_BN254_FR: c_int = 1;
@@ -165,6 +168,15 @@ extern "C" {
     pub fn ecg_batch_inverse_dev(ctx: *mut ecg_ctx, field_id: c_int, d_in: *const c_void, d_out: *mut c_void,
                                  n: usize, scale: *const u64, stream: *mut c_void) -> c_int;
     pub fn ecg_fr_scan_tile() -> usize;
+
+    // ---- fixed-base batch scalar multiplication (arkworks FixedBase::msm) ----
+    pub fn ecg_fixed_base_plan_info(curve_id: c_int, window_bits: u32, windows: *mut u32, row_entries: *mut u32,
+                                    table_bytes: *mut usize) -> c_int;
+    pub fn ecg_fixed_base_table(ctx: *mut ecg_ctx, curve_id: c_int, base_xy: *const u64, window_bits: u32,
+                                d_table: *mut *mut c_void) -> c_int;
+    pub fn ecg_fixed_base_mul_dev(ctx: *mut ecg_ctx, curve_id: c_int, d_table: *const c_void, window_bits: u32,
+                                  d_scalars: *const c_void, n: usize, flags: u32, d_out: *mut c_void,
+                                  stream: *mut c_void) -> c_int;
 
     // ---- EC-FFT (ec_fft.rs:56-164, 224-270) ----
     pub fn ecg_ec_fft(ctx: *mut ecg_ctx, curve_id: c_int, inout_jac: *mut u64, omega: *const u64, log_n: u32,
