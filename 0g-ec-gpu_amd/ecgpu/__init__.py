@@ -103,6 +103,8 @@ _SIGS = {
     "ecg_fixed_base_mul_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
                                               ctypes.c_void_p]),
+    "ecg_batch_mul_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "ecg_msm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, _u64p, ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
     "ecg_msm_multi": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, _u64p, _u64p,
                                      ctypes.c_size_t, _u64p, ABORT_CB, ctypes.c_void_p]),
@@ -701,6 +703,26 @@ def fixed_base_mul_dev(prog: Program, curve, table: FixedBaseTable, d_scalars, n
     _check(lib().ecg_fixed_base_mul_dev(prog.handle, cid, table.ptr, table.window, _dev_ptr(d_scalars), n,
                                         FB_SCALARS_MONTGOMERY if scalars_montgomery else 0, _dev_ptr(d_out), None),
            "fixed_base_mul_dev")
+    return d_out
+
+
+BM_SCALARS_MONTGOMERY, BM_ONE_SCALAR, BM_JACOBIAN = 1, 2, 4
+
+
+def batch_mul_dev(prog: Program, curve, d_points, d_scalars, n: int, d_out=None, *, scalars_montgomery: bool = False,
+                  one_scalar: bool = False, jacobian: bool = False) -> DeviceBuffer:
+    """out[i] = scalars[i] * points[i] over n HBM-resident G1 points (ecg_batch_mul_dev).
+    Points in and out are [x | y] base records (zeros = the identity), or Jacobian
+    (any Z in, (x, y, 1) / (0, 1, 0) out, as ec_fft_dev) with jacobian=True.
+    one_scalar: d_scalars holds one scalar for every point.  d_out may be d_points
+    (in place); None allocates.  The points must be in the prime-order subgroup."""
+    cid = _curve(curve)
+    if d_out is None:
+        d_out = DeviceBuffer(prog, max(n, 1) * (3 if jacobian else 2) * CURVE_FQ_LIMBS[cid] * 8)
+    flags = ((BM_SCALARS_MONTGOMERY if scalars_montgomery else 0) | (BM_ONE_SCALAR if one_scalar else 0)
+             | (BM_JACOBIAN if jacobian else 0))
+    _check(lib().ecg_batch_mul_dev(prog.handle, cid, _dev_ptr(d_points), _dev_ptr(d_scalars), n, flags,
+                                   _dev_ptr(d_out), None), "batch_mul_dev")
     return d_out
 
 

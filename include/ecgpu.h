@@ -262,6 +262,38 @@ int ecg_fixed_base_table(ecg_ctx *ctx, int curve_id, const uint64_t *base_xy /* 
 int ecg_fixed_base_mul_dev(ecg_ctx *ctx, int curve_id, const void *d_table, uint32_t window_bits,
                            const void *d_scalars, size_t n, uint32_t flags, void *d_out, void *stream);
 
+/* ---- variable-base batch scalar multiplication (G1) --------------------------
+ * out_i = s_i * P_i for n device-resident points and scalars, a different point
+ * per scalar: the element-wise product between the EC-FFTs of an FK20 / AMT
+ * proof, the n^-1 that finishes an inverse EC-FFT, [gamma^i] P_i before
+ * ecg_msm_prepare_bases, a commitment vector folded by a challenge vector.
+ * curve_id is ECG_CURVE_BLS12_381 or ECG_CURVE_BN254 (G2 ids are
+ * ECG_ERR_INVALID).  One launch: per point a GLV split k = k1 + k2 * lambda, one
+ * table m * P (m = 1..8) and a joint chain of 128 doublings and 66 complete
+ * additions over signed 4-bit windows, normalised with one field inversion per
+ * 512 outputs.  The workspace (the resident lanes' tables, about
+ * 220 MB) does not depend on n; ecg_ctx_release_workspace frees it.
+ * The points MUST lie in the prime-order subgroup, as for the EC-FFT: the
+ * endomorphism phi(x, y) = (beta x, y) equals lambda * P only there.  The call
+ * does not check it (nor that a point is on the curve). */
+#define ECG_BM_SCALARS_MONTGOMERY 1  /* d_scalars are Fr Montgomery elements */
+#define ECG_BM_ONE_SCALAR 2          /* d_scalars holds ONE scalar, applied to every point */
+#define ECG_BM_JACOBIAN 4            /* points in and out are Jacobian [X, Y, Z] (3 x Lq u64), as the EC-FFT's */
+
+/* d_points: n base records [x, y] (2 x Lq u64, Montgomery; the all-zero record
+ * is the identity) -- what ecg_fixed_base_mul_dev writes and ecg_msm_dev reads;
+ * d_out gets n records of the same form, fully reduced.  With ECG_BM_JACOBIAN
+ * both are Jacobian: any Z in (Z = 0 is the identity), normalised (x, y, 1) /
+ * (0, 1, 0) out, exactly what ecg_ec_fft_dev leaves.  d_scalars: n BigInt<4>
+ * (any 256-bit word is reduced mod r), Montgomery Fr elements with
+ * ECG_BM_SCALARS_MONTGOMERY, one element instead of n with ECG_BM_ONE_SCALAR.
+ * d_out == d_points (in place) is allowed; any other overlap of d_out with an
+ * input, and unknown flag bits, are ECG_ERR_INVALID.  n = 0 returns ECG_OK and
+ * touches nothing; n <= 2^32.  `stream` is a hipStream_t; NULL = the context's
+ * stream, and the call then waits for the result. */
+int ecg_batch_mul_dev(ecg_ctx *ctx, int curve_id, const void *d_points, const void *d_scalars, size_t n,
+                      uint32_t flags, void *d_out, void *stream);
+
 /* ---- EC-FFT (FFT over G1, "FFTg") -------------------------------------------
  * In-place DFT of 2^log_n G1 points: P_k <- sum_j omega^(j k) * P_j, natural
  * order in and out, omega an Fr element (Montgomery, 4 x u64) that is a

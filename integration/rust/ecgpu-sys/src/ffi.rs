@@ -57,6 +57,11 @@ pub const ECG_POLY_OUT_CANONICAL: c_int = 1;
 // ecg_fixed_base_mul_dev flags
 pub const ECG_FB_SCALARS_MONTGOMERY: c_int = 1;
 
+// ecg_batch_mul_dev flags
+pub const ECG_BM_SCALARS_MONTGOMERY: c_int = 1;
+pub const ECG_BM_ONE_SCALAR: c_int = 2;
+pub const ECG_BM_JACOBIAN: c_int = 4;
+
 // ---- ecg_rr_ops layouts and ops ------------------------------------------------
 pub const ECG_RR_BLS12_381_FR: c_int = 0;
 pub const ECG_RR_BN254_FR: c_int = 1;
@@ -177,6 +182,10 @@ extern "C" {
     pub fn ecg_fixed_base_mul_dev(ctx: *mut ecg_ctx, curve_id: c_int, d_table: *const c_void, window_bits: u32,
                                   d_scalars: *const c_void, n: usize, flags: u32, d_out: *mut c_void,
                                   stream: *mut c_void) -> c_int;
+
+    // ---- variable-base batch scalar multiplication: out_i = s_i * P_i ----
+    pub fn ecg_batch_mul_dev(ctx: *mut ecg_ctx, curve_id: c_int, d_points: *const c_void, d_scalars: *const c_void,
+                             n: usize, flags: u32, d_out: *mut c_void, stream: *mut c_void) -> c_int;
 
     // ---- EC-FFT (ec_fft.rs:56-164, 224-270) ----
     pub fn ecg_ec_fft(ctx: *mut ecg_ctx, curve_id: c_int, inout_jac: *mut u64, omega: *const u64, log_n: u32,
