@@ -96,6 +96,11 @@ _SIGS = {
     "ecg_batch_inverse_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_size_t, _u64p, ctypes.c_void_p]),
     "ecg_fr_scan_tile": (ctypes.c_size_t, []),
+    "ecg_fr_lincomb_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32,
+                                          ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _u64p,
+                                          ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.c_void_p, _u64p,
+                                          ctypes.c_uint32, ctypes.c_void_p]),
+    "ecg_fr_lincomb_tile": (ctypes.c_size_t, []),
     "ecg_fixed_base_plan_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                                 ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)]),
     "ecg_fixed_base_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, ctypes.c_uint32,
@@ -648,6 +653,40 @@ def batch_inverse_dev(prog: Program, field, d_in, n: int, d_out=None, *, scale=N
 def fr_scan_tile() -> int:
     """Elements per workgroup tile of poly_div_linear_dev / batch_inverse_dev."""
     return int(lib().ecg_fr_scan_tile())
+
+
+FRV_OUT_CANONICAL = 1
+FRV_MAX_TERMS = 8
+
+
+def fr_lincomb_dev(prog: Program, field, n: int, terms, d_out=None, *, ratio=None, index0=0, canonical=False,
+                   want_sum=False, geo_mask=None, flags=None):
+    """out[i] = sum_j c_j * a_j[i] * b_j[i] * (ratio^(index0 + i) if geo_j else 1) over HBM-resident
+    Montgomery Fr (ecg_fr_lincomb_dev).  terms: up to 8 of (coeff | None, a | None, b | None, geo);
+    None stands for 1; a, b are DeviceBuffers or raw device addresses, and d_out may be one of
+    them (in place) or None (total only).  canonical: out and the total leave Montgomery form.
+    Returns the total (4 x u64; the call then synchronises) with want_sum, else None."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    k = len(terms)
+    arr = ctypes.c_void_p * max(k, 1)
+    d_a = arr(*[None if t[1] is None else _dev_ptr(t[1]) for t in terms])
+    d_b = arr(*[None if t[2] is None else _dev_ptr(t[2]) for t in terms])
+    coeffs = None
+    if any(t[0] is not None for t in terms):
+        one = fr_mont_from_int(fid, 1)
+        coeffs = np.ascontiguousarray(np.stack([one if t[0] is None else _fr_arg(t[0]) for t in terms]))
+    gm = sum(1 << j for j, t in enumerate(terms) if t[3]) if geo_mask is None else int(geo_mask)
+    fl = (FRV_OUT_CANONICAL if canonical else 0) if flags is None else int(flags)
+    total = np.zeros(4, dtype=np.uint64) if want_sum else None
+    _check(lib().ecg_fr_lincomb_dev(prog.handle, fid, n, k, d_a, d_b, _fr_ptr(coeffs), gm, _fr_ptr(_fr_arg(ratio)),
+                                    index0, None if d_out is None else _dev_ptr(d_out), _fr_ptr(total), fl, None),
+           "fr_lincomb_dev")
+    return total
+
+
+def fr_lincomb_tile() -> int:
+    """Elements per workgroup tile of fr_lincomb_dev."""
+    return int(lib().ecg_fr_lincomb_tile())
 
 
 FB_SCALARS_MONTGOMERY = 1

@@ -226,6 +226,35 @@ int ecg_batch_inverse_dev(ecg_ctx *ctx, int field_id, const void *d_in, void *d_
 /* Elements per workgroup tile of the two calls above (tests place their sizes around its multiples). */
 size_t ecg_fr_scan_tile(void);
 
+/* Fused sum of products over resident Fr vectors, the step between the calls above and the
+ * transforms (arkworks: the element-wise operators of DensePolynomial / Evaluations and
+ * EvaluationDomain::distribute_powers, one pass over memory per call instead of one per operator):
+ *   out[i] = sum_{j<k} c_j * A_j[i] * B_j[i] * G_j(i),   0 <= i < n,
+ *   G_j(i) = g^(index0 + i) if bit j of geo_mask is set, else 1;   sum = sum_i out[i].
+ * d_a, d_b: k device pointers each (n x 32 B, Montgomery, 16-byte aligned); the array or an entry
+ * may be NULL, which stands for the constant 1.  coeffs: k x 4 u64, host, Montgomery, < r; NULL =
+ * all ones.  ratio g: host, Montgomery, < r, needed iff geo_mask != 0; one ratio per call.
+ * index0 + n <= 2^32 (a slice or a rank's shard of a longer vector).
+ * d_out may be NULL (total only) and may BE any of the operands (in place: the operation is
+ * element-wise); any partial overlap is ECG_ERR_INVALID.  sum_out (host, 4 x u64, may be NULL)
+ * receives the total; the call synchronises only then.  ECG_FRV_OUT_CANONICAL: out and sum leave
+ * Montgomery form.  A vector named several times is read once.  k = 0 or k > ECG_FRV_MAX_TERMS,
+ * a geo_mask bit at or above k, geo_mask without ratio, d_out and sum_out both NULL, unknown
+ * flags, a coefficient or ratio >= r and a misaligned pointer are ECG_ERR_INVALID.  n = 0 is
+ * ECG_OK, touches nothing and gives sum 0.  Workspace: 48 B per workgroup ("fr_vec_*"). */
+#define ECG_FRV_OUT_CANONICAL 1u  /* out and sum leave Montgomery form (BigInt<4>: MSM / batch_mul scalars) */
+#define ECG_FRV_MAX_TERMS 8
+int ecg_fr_lincomb_dev(ecg_ctx *ctx, int field_id, size_t n, uint32_t k,
+                       const void *const *d_a, const void *const *d_b,
+                       const uint64_t *coeffs,
+                       uint32_t geo_mask, const uint64_t *ratio,
+                       size_t index0,
+                       void *d_out,
+                       uint64_t *sum_out,
+                       uint32_t flags, void *stream);
+/* Elements per workgroup tile of ecg_fr_lincomb_dev (tests and callers that size slices). */
+size_t ecg_fr_lincomb_tile(void);
+
 /* ---- fixed-base batch scalar multiplication (G1) -----------------------------
  * out_i = s_i * B for n device-resident scalars and ONE base B: arkworks'
  * FixedBase::msm / batch_mul, the step that makes a structured reference

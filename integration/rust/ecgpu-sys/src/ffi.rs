@@ -54,6 +54,10 @@ pub const ECG_FOP_INV: c_int = 8;
 // ecg_poly_div_linear_dev flags
 pub const ECG_POLY_OUT_CANONICAL: c_int = 1;
 
+// ecg_fr_lincomb_dev: flag and the largest k
+pub const ECG_FRV_OUT_CANONICAL: c_int = 1;
+pub const ECG_FRV_MAX_TERMS: c_int = 8;
+
 // ecg_fixed_base_mul_dev flags
 pub const ECG_FB_SCALARS_MONTGOMERY: c_int = 1;
 
@@ -173,6 +177,12 @@ extern "C" {
     pub fn ecg_batch_inverse_dev(ctx: *mut ecg_ctx, field_id: c_int, d_in: *const c_void, d_out: *mut c_void,
                                  n: usize, scale: *const u64, stream: *mut c_void) -> c_int;
     pub fn ecg_fr_scan_tile() -> usize;
+    // fused sum of products over resident Fr vectors: d_a / d_b are k device pointers each (null = 1)
+    pub fn ecg_fr_lincomb_dev(ctx: *mut ecg_ctx, field_id: c_int, n: usize, k: u32, d_a: *const *const c_void,
+                              d_b: *const *const c_void, coeffs: *const u64, geo_mask: u32, ratio: *const u64,
+                              index0: usize, d_out: *mut c_void, sum_out: *mut u64, flags: u32,
+                              stream: *mut c_void) -> c_int;
+    pub fn ecg_fr_lincomb_tile() -> usize;
 
     // ---- fixed-base batch scalar multiplication (arkworks FixedBase::msm) ----
     pub fn ecg_fixed_base_plan_info(curve_id: c_int, window_bits: u32, windows: *mut u32, row_entries: *mut u32,
