@@ -46,69 +46,18 @@
 //   Sk carried sum (rr_add: QN) of value < k p.
 // The tightest slack is BLS12-381 Fr's: a b <= 2^6 p^2 / 2 = 32 p^2.  Aggregates
 // and carries go to memory through rr_reduce_q (< 1.1 p, exact limbs: "N").
+// The geometry constants, the table, the limb / lane helpers, the division's
+// wave reduce and block scan and the host side of the R' form are in
+// fr_scan.hpp, shared with fr_div_binomial.hip.
 #include <cstring>
 
 #include "ctx.hpp"
 #include "fieldrr.hpp"
 #include "fieldrr_inv.hpp"
+#include "fr_scan.hpp"
 #include "host_field.hpp"
 
 namespace ecg {
-
-constexpr int FRS_THREADS = 256;                      // threads per tile
-constexpr int FRS_E = 8;                              // consecutive elements per thread
-constexpr int FRS_LOG_TILE = 11;                      // 2048 elements per tile
-constexpr int FRS_TILE = 1 << FRS_LOG_TILE;
-constexpr int FRS_WAVES = FRS_THREADS / 64;
-constexpr int FRS_SLOTS = 2 * FRS_TILE + 2 * FRS_TILE / 16;  // uint4 slots with the padding
-constexpr int FRS_SCAN_THREADS = 1024;                // the scan kernel's one workgroup
-constexpr int FRS_SCAN_WAVES = FRS_SCAN_THREADS / 64;
-constexpr int FRS_NPOW = 30;                          // z^(2^k), k < 30
-constexpr int FRS_MAX_LOG_RUN = FRS_NPOW - 1 - 6 - FRS_LOG_TILE;  // the block scan reads pw[11 + lgR + 6]
-static_assert(FRS_THREADS * FRS_E == FRS_TILE && FRS_E == 8, "a thread's run is 16 uint4 slots");
-
-// Kernel-argument table (wave-uniform): pw[k] = z^(2^k) in the R' form (C);
-// cst = R' / R (ECG_POLY_OUT_CANONICAL) or K = scale R^2 / R' (inversion).
-struct FrsTable {
-  uint32_t pw[FRS_NPOW][9];
-  uint32_t cst[9];
-};
-
-template <class Q>
-ECG_DEV FpR<Q> frs_limbs(const uint32_t* p) {
-  static_assert(Q::NL == 9, "Fr layouts: 9 limbs");
-  FpR<Q> r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.v[i] = p[i];
-  return r;
-}
-template <class Q>
-ECG_DEV void frs_put_limbs(uint32_t* p, const FpR<Q>& a) {
-#pragma unroll
-  for (int i = 0; i < 9; i++) p[i] = a.v[i];
-}
-template <class Q>
-ECG_DEV FpR<Q> frs_pick(bool c, const FpR<Q>& a, const FpR<Q>& b) {
-  FpR<Q> r;
-#pragma unroll
-  for (int i = 0; i < Q::NL; i++) r.v[i] = c ? a.v[i] : b.v[i];
-  return r;
-}
-// the value of lane + d (DOWN) / lane - d (UP); a lane without a partner reads itself
-template <bool DOWN, class Q>
-ECG_DEV FpR<Q> frs_shift(const FpR<Q>& a, int d) {
-  FpR<Q> r;
-#pragma unroll
-  for (int i = 0; i < Q::NL; i++) r.v[i] = DOWN ? __shfl_down(a.v[i], d, 64) : __shfl_up(a.v[i], d, 64);
-  return r;
-}
-template <class Q>
-ECG_DEV FpR<Q> frs_bcast(const FpR<Q>& a, int lane) {
-  FpR<Q> r;
-#pragma unroll
-  for (int i = 0; i < Q::NL; i++) r.v[i] = __shfl(a.v[i], lane, 64);
-  return r;
-}
 
 // ---------------------------------------------------------------------------
 // tile staging: global <-> LDS as consecutive uint4, thread runs out of LDS
@@ -158,12 +107,6 @@ ECG_DEV void frs_put(uint4* lds, int k, const FpR<Q>& c) {
   lds[s] = make_uint4(w[0], w[1], w[2], w[3]);
   lds[s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
-// lazy value (QN, < 64 p) -> canonical limbs
-template <class Q>
-ECG_DEV FpR<Q> frs_canon(const FpR<Q>& a) {
-  return rr_canon_lt2p(rr_reduce_q(a));
-}
-
 // ---------------------------------------------------------------------------
 // division: h_left + M^len h_right with uniform multipliers
 // ---------------------------------------------------------------------------
@@ -174,58 +117,6 @@ ECG_DEV FpR<Q> frs_div_run(const uint4* lds, const FpR<Q>& z) {
 #pragma unroll
   for (int k = FRS_E - 2; k >= 0; k--) h = rr_add(frs_get<Q>(lds, k), rr_mul(h, z));  // (C | S2.5) x C -> C + M
   return h;
-}
-
-// Wave reduce: lane 0 ends with sum_l g_l M^l, M = pw[m0] (a run's length as a
-// power of z).  g S4.1 on entry, S13.1 after six levels; every lane computes.
-template <class Q>
-ECG_DEV FpR<Q> frs_div_wave_reduce(FpR<Q> g, const FrsTable& tab, int m0) {
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const FpR<Q> o = frs_shift<true>(g, 1 << k);
-    g = rr_add(g, rr_mul(o, frs_limbs<Q>(tab.pw[m0 + k])));  // S13.1 x C = 13.1 p^2 -> M
-  }
-  return g;
-}
-
-// Block scan: X_i = sum_{j > i} g_j M^(j-i-1) + M^(threads-1-i) carry_in, the
-// value that follows thread i's run.  g S2.6, carry_in N.
-//  1. wave totals (tree reduce), broadcast and stored by every lane, N;
-//  2. this wave's carry c = sum over the later waves (Horner, M^64) + carry_in:
-//     N + M = S2.6, a wave-uniform trip count;
-//  3. lane 63 takes g + M c (S4.1); every lane computes, a select keeps it;
-//  4. inclusive suffix scan, six levels (S13.1); the exclusive value is the
-//     next lane's, lane 63 takes c.
-template <class Q, int NW>
-ECG_DEV FpR<Q> frs_div_block_scan(FpR<Q> g, const FpR<Q>& carry_in, const FrsTable& tab, int m0,
-                                  uint32_t (*wagg)[9]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const FpR<Q> tot = rr_reduce_q(frs_bcast(frs_div_wave_reduce(g, tab, m0), 0));
-  frs_put_limbs(wagg[wave], tot);
-  __syncthreads();
-  FpR<Q> c = carry_in;
-  for (int u = NW - 1; u > wave; u--)
-    c = rr_add(frs_limbs<Q>(wagg[u]), rr_mul(c, frs_limbs<Q>(tab.pw[m0 + 6])));  // N + (N | S2.6) x C
-  const FpR<Q> gi = rr_add(g, rr_mul(c, frs_limbs<Q>(tab.pw[m0])));              // S2.6 + S2.6 x C
-  g = frs_pick(lane == 63, gi, g);
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const FpR<Q> o = frs_shift<true>(g, 1 << k);
-    const FpR<Q> s = rr_add(g, rr_mul(o, frs_limbs<Q>(tab.pw[m0 + k])));  // S13.1 x C -> M
-    g = frs_pick(lane + (1 << k) < 64, s, g);
-  }
-  const FpR<Q> x = frs_shift<true>(g, 1);
-  __syncthreads();  // wagg may be written again
-  return frs_pick(lane == 63, c, x);
-}
-
-// lazy s R (QN, < 64 p) -> the output words: canonical s R, or s (one product by R' / R)
-template <class Q, bool CANON>
-ECG_DEV FpR<Q> frs_div_out(const FpR<Q>& s, const FrsTable& tab) {
-  if constexpr (CANON)
-    return rr_canon_lt2p(rr_mul(s, frs_limbs<Q>(tab.cst)));  // S13.1 x C -> M
-  else
-    return frs_canon(s);
 }
 
 template <class Q>
@@ -421,46 +312,8 @@ __global__ void __launch_bounds__(FRS_THREADS)
 
 
 // ---------------------------------------------------------------------------
-// host side: the uniform table (host_field.hpp), workspace, launches
+// host side: the uniform table (fr_scan.hpp, host_field.hpp), workspace, launches
 // ---------------------------------------------------------------------------
-template <class P, class Q>
-static host::HFp<P> frs_from_limbs(const uint32_t* limbs) {  // sum limbs[i] 2^(BITS i), < 2^(64 N)
-  host::HFp<P> r = host::HFp<P>::zero();
-  for (int i = 0; i < Q::NL; i++) {
-    const int bit = Q::BITS * i, w = bit >> 6, s = bit & 63;
-    r.v[w] |= (uint64_t)limbs[i] << s;
-    if (s + Q::BITS > 64 && w + 1 < P::N) r.v[w + 1] |= (uint64_t)limbs[i] >> (64 - s);
-  }
-  return r;
-}
-template <class P, class Q>
-static void frs_to_limbs(const host::HFp<P>& x, uint32_t* limbs) {
-  for (int i = 0; i < Q::NL; i++) {
-    const int bit = Q::BITS * i, w = bit >> 6, s = bit & 63;
-    uint64_t v = x.v[w] >> s;
-    if (s + Q::BITS > 64 && w + 1 < P::N) v |= x.v[w + 1] << (64 - s);
-    limbs[i] = (uint32_t)v & ((1u << Q::BITS) - 1);
-  }
-}
-// x -> x R' / R: a Montgomery word v R becomes v R', the R' form of v (hmul(a, b) = a b / R)
-template <class P, class Q>
-static void frs_to_rr(const host::HFp<P>& x, uint32_t* limbs) {
-  frs_to_limbs<P, Q>(host::hmul(x, frs_from_limbs<P, Q>(Q::ONE)), limbs);
-}
-
-template <class P>
-static bool frs_below_r(const uint64_t* v) {
-  for (int i = P::N - 1; i >= 0; i--)
-    if (v[i] != P::P[i]) return v[i] < P::P[i];
-  return false;
-}
-
-static uint32_t frs_lg_run(size_t ntiles) {  // smallest power-of-two run with which 1024 threads cover the tiles
-  uint32_t lg = 0;
-  while (((size_t)FRS_SCAN_THREADS << lg) < ntiles) lg++;
-  return lg;
-}
-
 template <class P, class Q>
 static int frs_div_t(ecg_ctx* ctx, const void* d_coeffs, size_t n, const uint64_t* z, void* d_out,
                      uint64_t* value_out, bool canonical, hipStream_t s) {
@@ -538,25 +391,6 @@ static int frs_inv_t(ecg_ctx* ctx, const void* d_in, void* d_out, size_t n, cons
   hipLaunchKernelGGL(frs_inv_apply_kernel<Q>, dim3((uint32_t)ntiles), dim3(FRS_THREADS), 0, s, (const uint4*)d_in, n,
                      (const F*)pfx, (const F*)inv, (uint4*)d_out);
   ECG_HIP(hipGetLastError());
-  return ECG_OK;
-}
-
-// shared argument checks; 1 = nothing to do (n == 0)
-static int frs_check(const char* what, int field_id, const void* d_in, size_t n) {
-  if (field_id != ECG_FIELD_BLS12_381_FR && field_id != ECG_FIELD_BN254_FR) {
-    set_error("%s: field_id %d is not a scalar field (bls12_381_fr, bn254_fr)", what, field_id);
-    return ECG_ERR_INVALID;
-  }
-  if (n == 0) return 1;
-  if (!d_in) {
-    set_error("%s: null pointer", what);
-    return ECG_ERR_INVALID;
-  }
-  static_assert(32 - FRS_LOG_TILE - 10 <= FRS_MAX_LOG_RUN, "2^32 elements: 1024 threads x 2^FRS_MAX_LOG_RUN tiles");
-  if (n >> 32) {
-    set_error("%s: n = %zu is above 2^32", what, n);
-    return ECG_ERR_INVALID;
-  }
   return ECG_OK;
 }
 

@@ -96,6 +96,11 @@ _SIGS = {
     "ecg_batch_inverse_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_size_t, _u64p, ctypes.c_void_p]),
     "ecg_fr_scan_tile": (ctypes.c_size_t, []),
+    "ecg_poly_div_binomial_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                                 ctypes.c_uint32, _u64p, ctypes.c_void_p, ctypes.c_uint32,
+                                                 ctypes.c_void_p]),
+    "ecg_poly_div_binomial_plan": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
+                                                  ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)]),
     "ecg_fr_lincomb_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32,
                                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _u64p,
                                           ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.c_void_p, _u64p,
@@ -639,6 +644,31 @@ def poly_div_linear_dev(prog: Program, field, d_coeffs, n: int, z: np.ndarray, d
                                          None if d_out is None else _dev_ptr(d_out), _fr_ptr(val), fl, None),
            "poly_div_linear_dev")
     return val
+
+
+DIVB_PATH_LINEAR, DIVB_PATH_STRIDED, DIVB_PATH_COLUMNS = 0, 1, 2
+
+
+def poly_div_binomial_dev(prog: Program, field, d_coeffs, n: int, log_m: int, c: np.ndarray, d_out=None, *,
+                          canonical=False, flags=None) -> None:
+    """p(X) = q(X)(X^m - c) + rem(X), m = 2^log_m, over HBM-resident coefficients
+    (ecg_poly_div_binomial_dev): d_out[:m] = rem, d_out[m:] = q; d_out=None: in place.
+    c: Montgomery Fr (4 x u64).  canonical: outputs leave Montgomery form.  Does not synchronise."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    cc = _fr_arg(c)
+    fl = (POLY_OUT_CANONICAL if canonical else 0) if flags is None else int(flags)
+    _check(lib().ecg_poly_div_binomial_dev(prog.handle, fid, _dev_ptr(d_coeffs), n, int(log_m), _fr_ptr(cc),
+                                           _dev_ptr(d_coeffs if d_out is None else d_out), fl, None),
+           "poly_div_binomial_dev")
+
+
+def poly_div_binomial_plan(n: int, log_m: int):
+    """(path, segments, rows_per_segment) of poly_div_binomial_dev(n, log_m): path is one of
+    DIVB_PATH_*; the split along a column chain is tiles and rows per tile, or row segments."""
+    p, s, r = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_size_t()
+    _check(lib().ecg_poly_div_binomial_plan(int(n), int(log_m), ctypes.byref(p), ctypes.byref(s), ctypes.byref(r)),
+           "poly_div_binomial_plan")
+    return p.value, s.value, r.value
 
 
 def batch_inverse_dev(prog: Program, field, d_in, n: int, d_out=None, *, scale=None) -> None:

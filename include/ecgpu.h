@@ -226,6 +226,31 @@ int ecg_batch_inverse_dev(ecg_ctx *ctx, int field_id, const void *d_in, void *d_
 /* Elements per workgroup tile of the two calls above (tests place their sizes around its multiples). */
 size_t ecg_fr_scan_tile(void);
 
+/* Division of p (n coefficients, ascending, Montgomery Fr, device memory) by the binomial
+ * X^m - c, m = 2^log_m: the vanishing polynomial of a subgroup or coset of size m (ark-poly's
+ * divide_by_vanishing_poly, the quotient of a KZG multi-point opening over a coset, one level
+ * of an AMT).  d_out gets n elements, d_out[j] = s_j with s_j = p_j + c s_(j+m) and s_j = 0 for
+ * j >= n: d_out[0..m) is the remainder p mod (X^m - c) and d_out[m + j] = q_j, the convention
+ * of ecg_poly_div_linear_dev, whose bytes the call returns at log_m = 0.
+ * n: 1 to 2^32, any value (not only multiples of m); n = 0 returns ECG_OK and touches nothing.
+ * log_m: 0 to 31; m >= n is legal (empty quotient, d_out = p).  c: host, Montgomery, < r; c = 0
+ * is legal (d_out = p).  d_out == d_coeffs (in place) is allowed; any other overlap, d_out ==
+ * NULL, log_m > 31, c >= r and unknown flag bits are ECG_ERR_INVALID.  flags:
+ * ECG_POLY_OUT_CANONICAL.  The call does not synchronise.  Workspace: "fr_scan_*", at most
+ * 7 % of the input (ecg_ctx_release_workspace frees it). */
+int ecg_poly_div_binomial_dev(ecg_ctx *ctx, int field_id, const void *d_coeffs, size_t n,
+                              uint32_t log_m, const uint64_t *c, void *d_out,
+                              uint32_t flags, void *stream);
+
+/* The plan the call above runs for (n, log_m), host only.  segments and rows_per_segment are
+ * the split along a column chain: tiles per chain and matrix rows per tile (linear and strided
+ * paths), row segments and their length (column path; one segment = a single launch). */
+#define ECG_DIVB_PATH_LINEAR 0   /* log_m = 0: ecg_poly_div_linear_dev */
+#define ECG_DIVB_PATH_STRIDED 1  /* small m: tile scan over strided runs */
+#define ECG_DIVB_PATH_COLUMNS 2  /* large m: independent columns, row segments */
+int ecg_poly_div_binomial_plan(size_t n, uint32_t log_m, int *path, uint32_t *segments,
+                               size_t *rows_per_segment);
+
 /* Fused sum of products over resident Fr vectors, the step between the calls above and the
  * transforms (arkworks: the element-wise operators of DensePolynomial / Evaluations and
  * EvaluationDomain::distribute_powers, one pass over memory per call instead of one per operator):

@@ -54,6 +54,11 @@ pub const ECG_FOP_INV: c_int = 8;
 // ecg_poly_div_linear_dev flags
 pub const ECG_POLY_OUT_CANONICAL: c_int = 1;
 
+// ecg_poly_div_binomial_plan paths
+pub const ECG_DIVB_PATH_LINEAR: c_int = 0;
+pub const ECG_DIVB_PATH_STRIDED: c_int = 1;
+pub const ECG_DIVB_PATH_COLUMNS: c_int = 2;
+
 // ecg_fr_lincomb_dev: flag and the largest k
 pub const ECG_FRV_OUT_CANONICAL: c_int = 1;
 pub const ECG_FRV_MAX_TERMS: c_int = 8;
@@ -177,6 +182,12 @@ extern "C" {
     pub fn ecg_batch_inverse_dev(ctx: *mut ecg_ctx, field_id: c_int, d_in: *const c_void, d_out: *mut c_void,
                                  n: usize, scale: *const u64, stream: *mut c_void) -> c_int;
     pub fn ecg_fr_scan_tile() -> usize;
+    // division by X^m - c, m = 2^log_m (d_out[0..m) the remainder, the rest the quotient), and its plan
+    pub fn ecg_poly_div_binomial_dev(ctx: *mut ecg_ctx, field_id: c_int, d_coeffs: *const c_void, n: usize,
+                                     log_m: u32, c: *const u64, d_out: *mut c_void, flags: u32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn ecg_poly_div_binomial_plan(n: usize, log_m: u32, path: *mut c_int, segments: *mut u32,
+                                      rows_per_segment: *mut usize) -> c_int;
     // fused sum of products over resident Fr vectors: d_a / d_b are k device pointers each (null = 1)
     pub fn ecg_fr_lincomb_dev(ctx: *mut ecg_ctx, field_id: c_int, n: usize, k: u32, d_a: *const *const c_void,
                               d_b: *const *const c_void, coeffs: *const u64, geo_mask: u32, ratio: *const u64,
