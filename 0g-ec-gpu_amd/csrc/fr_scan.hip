@@ -46,9 +46,10 @@
 //   Sk carried sum (rr_add: QN) of value < k p.
 // The tightest slack is BLS12-381 Fr's: a b <= 2^6 p^2 / 2 = 32 p^2.  Aggregates
 // and carries go to memory through rr_reduce_q (< 1.1 p, exact limbs: "N").
-// The geometry constants, the table, the limb / lane helpers, the division's
-// wave reduce and block scan and the host side of the R' form are in
-// fr_scan.hpp, shared with fr_div_binomial.hip.
+// The geometry constants, the table, the limb / lane helpers, the tile staging,
+// the division's wave reduce and block scan, the product block scan and the
+// host side of the R' form are in fr_scan.hpp, shared with fr_div_binomial.hip
+// and fr_grand_product.hip.
 #include <cstring>
 
 #include "ctx.hpp"
@@ -59,54 +60,6 @@
 
 namespace ecg {
 
-// ---------------------------------------------------------------------------
-// tile staging: global <-> LDS as consecutive uint4, thread runs out of LDS
-// ---------------------------------------------------------------------------
-ECG_DEV uint32_t frs_slot(uint32_t j) { return j + (j >> 4); }
-
-ECG_DEV void frs_stage_in(const uint4* src, size_t tile, size_t n, uint4* lds) {
-  const size_t base = tile << FRS_LOG_TILE;
-#pragma unroll
-  for (int q = 0; q < 2 * FRS_E; q++) {
-    const uint32_t j = q * FRS_THREADS + threadIdx.x;
-    uint4 w = make_uint4(0, 0, 0, 0);
-    if (base + (j >> 1) < n) w = src[2 * base + j];
-    lds[frs_slot(j)] = w;
-  }
-}
-ECG_DEV void frs_stage_out(uint4* dst, size_t tile, size_t n, const uint4* lds) {
-  const size_t base = tile << FRS_LOG_TILE;
-#pragma unroll
-  for (int q = 0; q < 2 * FRS_E; q++) {
-    const uint32_t j = q * FRS_THREADS + threadIdx.x;
-    if (base + (j >> 1) < n) dst[2 * base + j] = lds[frs_slot(j)];
-  }
-}
-// element k of this thread's run: C (canonical input); zero = all-zero words
-template <class Q>
-ECG_DEV FpR<Q> frs_get(const uint4* lds, int k, bool& zero) {
-  const uint32_t s = 17 * threadIdx.x + 2 * k;
-  const uint4 lo = lds[s], hi = lds[s + 1];
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  zero = (lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) == 0;
-  FpR<Q> r;
-  rr_unpack<Q, 8>(w, r.v);
-  return r;
-}
-template <class Q>
-ECG_DEV FpR<Q> frs_get(const uint4* lds, int k) {
-  bool z;
-  return frs_get<Q>(lds, k, z);
-}
-// canonical limbs -> the thread's own slot k (read by frs_stage_out after a barrier)
-template <class Q>
-ECG_DEV void frs_put(uint4* lds, int k, const FpR<Q>& c) {
-  uint32_t w[8];
-  rr_pack<Q, 8>(c.v, w);
-  const uint32_t s = 17 * threadIdx.x + 2 * k;
-  lds[s] = make_uint4(w[0], w[1], w[2], w[3]);
-  lds[s + 1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
 // ---------------------------------------------------------------------------
 // division: h_left + M^len h_right with uniform multipliers
 // ---------------------------------------------------------------------------
@@ -188,36 +141,6 @@ __global__ void __launch_bounds__(FRS_THREADS)
 // ---------------------------------------------------------------------------
 // inversion: products (every operand C or M: at most 2.25 p^2 per product)
 // ---------------------------------------------------------------------------
-// element k of the run with zero read as 1
-template <class Q>
-ECG_DEV FpR<Q> frs_get_nz(const uint4* lds, int k, bool& zero) {
-  const FpR<Q> a = frs_get<Q>(lds, k, zero);
-  return frs_pick(zero, FpR<Q>::one(), a);
-}
-
-// Exclusive product scan over the block: the product of the g of every earlier
-// (UP) / later (DOWN) thread, 1 at the edge.  Wave scan by six levels, wave
-// totals through LDS (stored by every lane), then the other waves' totals
-// multiplied up with a wave-uniform trip count.
-template <class Q, int NW, bool DOWN>
-ECG_DEV FpR<Q> frs_mul_block_scan(const FpR<Q>& g, uint32_t (*wtot)[9]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  FpR<Q> v = g;
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const FpR<Q> s = rr_mul(v, frs_shift<DOWN>(v, 1 << k));  // M x M
-    v = frs_pick(DOWN ? lane + (1 << k) < 64 : lane >= (1 << k), s, v);
-  }
-  frs_put_limbs(wtot[wave], frs_bcast(v, DOWN ? 0 : 63));
-  const FpR<Q> e = frs_shift<DOWN>(v, 1);
-  __syncthreads();
-  FpR<Q> w = FpR<Q>::one();
-  for (int u = DOWN ? wave + 1 : 0; u < (DOWN ? NW : wave); u++) w = rr_mul(w, frs_limbs<Q>(wtot[u]));  // M x M
-  const FpR<Q> x = rr_mul(w, e);
-  __syncthreads();  // wtot may be written again
-  return frs_pick(DOWN ? lane == 63 : lane == 0, w, x);
-}
-
 template <class Q>
 __global__ void __launch_bounds__(FRS_THREADS)
     frs_inv_reduce_kernel(const uint4* __restrict__ a, size_t n, FpR<Q>* __restrict__ agg) {

@@ -101,6 +101,10 @@ _SIGS = {
                                                  ctypes.c_void_p]),
     "ecg_poly_div_binomial_plan": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int),
                                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)]),
+    "ecg_fr_grand_product_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32,
+                                                ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
+                                                ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_void_p, _u64p,
+                                                ctypes.c_uint32, ctypes.c_void_p]),
     "ecg_fr_lincomb_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32,
                                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _u64p,
                                           ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.c_void_p, _u64p,
@@ -683,6 +687,25 @@ def batch_inverse_dev(prog: Program, field, d_in, n: int, d_out=None, *, scale=N
 def fr_scan_tile() -> int:
     """Elements per workgroup tile of poly_div_linear_dev / batch_inverse_dev."""
     return int(lib().ecg_fr_scan_tile())
+
+
+def fr_grand_product_dev(prog: Program, field, n: int, nums, dens=(), d_out=None, *, init=None, canonical=False,
+                         want_total=False, flags=None):
+    """d_out[0] = init, d_out[i + 1] = d_out[i] * prod_j nums[j][i] / prod_j dens[j][i] over HBM-resident
+    Montgomery Fr (ecg_fr_grand_product_dev): the exclusive running product of column ratios; a zero
+    denominator gives the ratio 0.  nums: 1 to 4, dens: 0 to 4 DeviceBuffers or raw device addresses;
+    d_out may be one of them, None = in place over nums[0].  init: Montgomery Fr (4 x u64), None = 1.
+    canonical: d_out and the total leave Montgomery form.  Returns the product over all n elements
+    times init (4 x u64; the call then synchronises) with want_total, else None."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    d_num = (ctypes.c_void_p * max(len(nums), 1))(*[_dev_ptr(c) for c in nums])
+    d_den = (ctypes.c_void_p * max(len(dens), 1))(*[_dev_ptr(c) for c in dens])
+    fl = (1 if canonical else 0) if flags is None else int(flags)  # ECG_GP_OUT_CANONICAL
+    total = np.zeros(4, dtype=np.uint64) if want_total else None
+    _check(lib().ecg_fr_grand_product_dev(prog.handle, fid, n, len(nums), d_num, len(dens), d_den,
+                                          _fr_ptr(_fr_arg(init)), _dev_ptr(nums[0] if d_out is None else d_out),
+                                          _fr_ptr(total), fl, None), "fr_grand_product_dev")
+    return total
 
 
 FRV_OUT_CANONICAL = 1

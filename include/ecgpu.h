@@ -251,6 +251,33 @@ int ecg_poly_div_binomial_dev(ecg_ctx *ctx, int field_id, const void *d_coeffs, 
 int ecg_poly_div_binomial_plan(size_t n, uint32_t log_m, int *path, uint32_t *segments,
                                size_t *rows_per_segment);
 
+/* Grand product of column ratios, the running product z of permutation and lookup arguments
+ * (PLONK's z(X), plookup, the log-derivative checks' product form):
+ *   d_out[0] = init,   d_out[i + 1] = d_out[i] * f_i,   total = d_out[n - 1] * f_(n-1),
+ *   f_i = (prod_{j<k_num} num_j[i]) * inv0(prod_{j<k_den} den_j[i]),   inv0(0) = 0:
+ * a vanishing denominator gives the ratio 0, not an error (the zeros-kept rule of
+ * ecg_batch_inverse_dev), so everything after it is 0.  d_out is the EXCLUSIVE running product.
+ * d_num, d_den: host arrays of k_num (1 to ECG_GP_MAX_COLS) and k_den (0 to ECG_GP_MAX_COLS)
+ * device pointers, each to n x 32 B of Montgomery Fr < r; the same column may be named more than
+ * once.  k_den = 0 (d_den may be NULL) is the plain running product and runs no inversion;
+ * otherwise ONE field inversion per call: prefix products of the numerators and suffix products
+ * of the denominators around it, the three launches and the tile of the calls above.
+ * init: host, Montgomery, < r; NULL = 1.  total_out (host, 4 x u64, may be NULL) receives the
+ * product over all n elements times init; the call synchronises only then.
+ * ECG_GP_OUT_CANONICAL: d_out and the total leave Montgomery form.
+ * d_out may BE one of the columns (in place); any other overlap with a column is
+ * ECG_ERR_INVALID.  n: 1 to 2^32; n = 0 is ECG_OK, writes nothing and gives the total init.
+ * A non-scalar field, k_num = 0, a count above ECG_GP_MAX_COLS, a null column, array or d_out,
+ * init >= r and unknown flag bits are ECG_ERR_INVALID.  Every column is read twice:
+ * (2 (k_num + k_den) + 1) x 32 x n bytes.  Workspace: "fr_scan_*", about n / 2048 x 144 B. */
+#define ECG_GP_OUT_CANONICAL 1  /* d_out and the total leave Montgomery form */
+#define ECG_GP_MAX_COLS 4
+int ecg_fr_grand_product_dev(ecg_ctx *ctx, int field_id, size_t n,
+                             uint32_t k_num, const void *const *d_num,
+                             uint32_t k_den, const void *const *d_den,
+                             const uint64_t *init, void *d_out,
+                             uint64_t *total_out, uint32_t flags, void *stream);
+
 /* Fused sum of products over resident Fr vectors, the step between the calls above and the
  * transforms (arkworks: the element-wise operators of DensePolynomial / Evaluations and
  * EvaluationDomain::distribute_powers, one pass over memory per call instead of one per operator):

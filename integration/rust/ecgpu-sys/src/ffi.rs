@@ -59,6 +59,10 @@ pub const ECG_DIVB_PATH_LINEAR: c_int = 0;
 pub const ECG_DIVB_PATH_STRIDED: c_int = 1;
 pub const ECG_DIVB_PATH_COLUMNS: c_int = 2;
 
+// ecg_fr_grand_product_dev: flag and the most columns per side
+pub const ECG_GP_OUT_CANONICAL: c_int = 1;
+pub const ECG_GP_MAX_COLS: c_int = 4;
+
 // ecg_fr_lincomb_dev: flag and the largest k
 pub const ECG_FRV_OUT_CANONICAL: c_int = 1;
 pub const ECG_FRV_MAX_TERMS: c_int = 8;
@@ -188,6 +192,11 @@ extern "C" {
                                      stream: *mut c_void) -> c_int;
     pub fn ecg_poly_div_binomial_plan(n: usize, log_m: u32, path: *mut c_int, segments: *mut u32,
                                       rows_per_segment: *mut usize) -> c_int;
+    // grand product of column ratios (exclusive running product): d_num / d_den are k_num / k_den device pointers
+    pub fn ecg_fr_grand_product_dev(ctx: *mut ecg_ctx, field_id: c_int, n: usize, k_num: u32,
+                                    d_num: *const *const c_void, k_den: u32, d_den: *const *const c_void,
+                                    init: *const u64, d_out: *mut c_void, total_out: *mut u64, flags: u32,
+                                    stream: *mut c_void) -> c_int;
     // fused sum of products over resident Fr vectors: d_a / d_b are k device pointers each (null = 1)
     pub fn ecg_fr_lincomb_dev(ctx: *mut ecg_ctx, field_id: c_int, n: usize, k: u32, d_a: *const *const c_void,
                               d_b: *const *const c_void, coeffs: *const u64, geo_mask: u32, ratio: *const u64,
