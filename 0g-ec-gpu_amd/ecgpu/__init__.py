@@ -110,6 +110,15 @@ _SIGS = {
                                           ctypes.c_uint32, _u64p, ctypes.c_size_t, ctypes.c_void_p, _u64p,
                                           ctypes.c_uint32, ctypes.c_void_p]),
     "ecg_fr_lincomb_tile": (ctypes.c_size_t, []),
+    "ecg_fr_sumcheck_round_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, _u32p, _u32p, _u64p,
+                                                 _u64p, ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_uint32,
+                                                 ctypes.c_void_p]),
+    "ecg_fr_sumcheck_tile": (ctypes.c_size_t, []),
+    "ecg_fr_mle_fix_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, _u64p,
+                                          ctypes.c_uint32, ctypes.c_void_p, _u64p, ctypes.c_uint32, ctypes.c_void_p]),
+    "ecg_fr_eq_table_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, ctypes.c_uint32, _u64p,
+                                           ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "ecg_fixed_base_plan_info": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                                 ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_size_t)]),
     "ecg_fixed_base_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _u64p, ctypes.c_uint32,
@@ -740,6 +749,70 @@ def fr_lincomb_dev(prog: Program, field, n: int, terms, d_out=None, *, ratio=Non
 def fr_lincomb_tile() -> int:
     """Elements per workgroup tile of fr_lincomb_dev."""
     return int(lib().ecg_fr_lincomb_tile())
+
+
+SC_MAX_COLS, SC_MAX_PRODUCTS, SC_MAX_FACTORS = 8, 8, 4
+ML_OUT_CANONICAL = 1
+
+
+def _fr_rows(x, rows: int):
+    """rows Fr elements (Montgomery, rows x 4 u64) as a contiguous array, or None."""
+    return None if x is None else np.ascontiguousarray(x, dtype=np.uint64).reshape(rows, 4)
+
+
+def fr_sumcheck_round_dev(prog: Program, field, log_n: int, cols, products, *, coeffs=None, fold_r=None,
+                          d_folded=None, canonical=False, flags=None) -> np.ndarray:
+    """The round polynomial of sum_p c_p prod_{j in products[p]} cols[j] over HBM-resident Montgomery Fr
+    tables of 2^log_n entries (ecg_fr_sumcheck_round_dev): its values at t = 0 .. d, (d + 1) x 4 u64,
+    d = the longest product.  cols: up to 8 DeviceBuffers or raw device addresses; products: up to 8
+    tuples of 1 to 4 column indices; coeffs: one Montgomery Fr per product, None = all ones.  fold_r
+    (Montgomery Fr): every column is first bound to it (entries 2b, 2b + 1 pair), the bound tables go to
+    d_folded (one buffer of 2^(log_n - 1) entries per column) and the round runs on them.  canonical: the
+    values leave Montgomery form.  The call synchronises."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    d_cols = (ctypes.c_void_p * max(len(cols), 1))(*[_dev_ptr(c) for c in cols])
+    counts = np.array([len(p) for p in products], dtype=np.uint32)
+    fcols = np.array([j for p in products for j in p] or [0], dtype=np.uint32)
+    d_out = None if d_folded is None else (ctypes.c_void_p * max(len(d_folded), 1))(*[_dev_ptr(c) for c in d_folded])
+    cc = _fr_rows(coeffs, len(products))
+    evals = np.zeros((max(counts.tolist() or [0]) + 1, 4), dtype=np.uint64)
+    fl = (ML_OUT_CANONICAL if canonical else 0) if flags is None else int(flags)
+    _check(lib().ecg_fr_sumcheck_round_dev(prog.handle, fid, int(log_n), len(cols), d_cols, len(products),
+                                           counts.ctypes.data_as(_u32p), fcols.ctypes.data_as(_u32p), _fr_ptr(cc),
+                                           _fr_ptr(_fr_arg(fold_r)), d_out, _ptr(evals), fl, None),
+           "fr_sumcheck_round_dev")
+    return evals
+
+
+def fr_sumcheck_tile() -> int:
+    """Input elements per workgroup tile of fr_sumcheck_round_dev without fold_r."""
+    return int(lib().ecg_fr_sumcheck_tile())
+
+
+def fr_mle_fix_dev(prog: Program, field, d_in, log_n: int, point, d_out=None, *, canonical=False, flags=None):
+    """Binds x_0 .. x_(m-1) of an HBM-resident Montgomery Fr table of 2^log_n entries to the m rows of
+    point (m x 4 u64, Montgomery) in that order (ecg_fr_mle_fix_dev); d_out receives 2^(log_n - m)
+    entries.  At m = log_n this is the evaluation: d_out may be None, the value (4 x u64) is returned and
+    the call synchronises; otherwise returns None.  canonical: results leave Montgomery form."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+    m = len(pt)
+    val = np.zeros(4, dtype=np.uint64) if m == log_n else None
+    fl = (ML_OUT_CANONICAL if canonical else 0) if flags is None else int(flags)
+    _check(lib().ecg_fr_mle_fix_dev(prog.handle, fid, _dev_ptr(d_in), int(log_n), _ptr(pt), m,
+                                    None if d_out is None else _dev_ptr(d_out), _fr_ptr(val), fl, None),
+           "fr_mle_fix_dev")
+    return val
+
+
+def fr_eq_table_dev(prog: Program, field, point, d_out, *, scale=None, canonical=False, flags=None) -> None:
+    """d_out[i] = scale * prod_j (point[j] if bit j of i else 1 - point[j]) for the log_n rows of point
+    (log_n x 4 u64, Montgomery), i < 2^log_n (ecg_fr_eq_table_dev).  scale: Montgomery Fr, None = 1."""
+    fid = FIELD_NAMES.get(field, field) if isinstance(field, str) else int(field)
+    pt = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+    fl = (ML_OUT_CANONICAL if canonical else 0) if flags is None else int(flags)
+    _check(lib().ecg_fr_eq_table_dev(prog.handle, fid, _ptr(pt), len(pt), _fr_ptr(_fr_arg(scale)), _dev_ptr(d_out),
+                                     fl, None), "fr_eq_table_dev")
 
 
 FB_SCALARS_MONTGOMERY = 1

@@ -307,6 +307,65 @@ int ecg_fr_lincomb_dev(ecg_ctx *ctx, int field_id, size_t n, uint32_t k,
 /* Elements per workgroup tile of ecg_fr_lincomb_dev (tests and callers that size slices). */
 size_t ecg_fr_lincomb_tile(void);
 
+/* ---- multilinear Fr: evaluation tables on {0,1}^v --------------------------------
+ * What sumcheck provers (HyperPlonk, Spartan, GKR, multilinear KZG openings) run per round.
+ * Tables are 2^log_n x 32 B of Montgomery Fr < r in device memory, 16-byte aligned, indexed
+ * little-endian (i = sum x_j 2^j); as in ark-poly the entries 2b and 2b + 1 pair, so the LOWEST
+ * variable is bound first.  Scalar fields only; log_n: 1 to 32; stream as above.
+ *
+ * The round polynomial of a sum of products of tables (ark_linear_sumcheck's prove_round for a
+ * ListOfProductsOfPolynomials), with m = 2^log_n:
+ *   evals_out[t] = sum_{b < m/2} sum_p c_p prod_{j in S_p} (col_j[2b] + t (col_j[2b+1] - col_j[2b])),
+ *   t = 0 .. d,   d = max_p factor_counts[p].
+ * d_cols: k (1 to ECG_SC_MAX_COLS) device pointers.  Product p (n_products: 1 to
+ * ECG_SC_MAX_PRODUCTS) multiplies factor_counts[p] (1 to ECG_SC_MAX_FACTORS) columns, whose
+ * indices (< k) stand consecutively in factor_cols; one column may appear twice.  coeffs:
+ * n_products x 4 u64, host, Montgomery, < r; NULL = all ones.
+ * fold_r (host, Montgomery, < r; needs log_n >= 2 and d_folded): every column is first bound,
+ *   col'_j[b] = col_j[2b] + fold_r (col_j[2b+1] - col_j[2b]),   b < 2^(log_n - 1),
+ * col'_j is written to d_folded[j] (2^(log_n - 1) x 32 B, Montgomery) and the sums are taken over
+ * the col'_j: one pass does the k binds of the last round's challenge and this round.  d_folded[j]
+ * must not overlap any input or any other output.
+ * evals_out: host, (d + 1) x 4 u64, required; the call synchronises.  ECG_ML_OUT_CANONICAL: the
+ * evaluations (only) leave Montgomery form.  Counts out of range, a column index >= k, a null
+ * column, array or output, fold_r without d_folded, an overlap, a misaligned pointer, log_n out of
+ * range, a non-scalar field, a coefficient or challenge >= r and unknown flags are
+ * ECG_ERR_INVALID.  Workspace: 48 B per workgroup and t ("fr_ml_*"). */
+#define ECG_SC_MAX_COLS 8
+#define ECG_SC_MAX_PRODUCTS 8
+#define ECG_SC_MAX_FACTORS 4
+#define ECG_ML_OUT_CANONICAL 1  /* results leave Montgomery form */
+int ecg_fr_sumcheck_round_dev(ecg_ctx *ctx, int field_id, uint32_t log_n,
+                              uint32_t k, const void *const *d_cols,
+                              uint32_t n_products, const uint32_t *factor_counts,
+                              const uint32_t *factor_cols, const uint64_t *coeffs,
+                              const uint64_t *fold_r, void *const *d_folded,
+                              uint64_t *evals_out, uint32_t flags, void *stream);
+/* Input elements per workgroup tile of the round above without fold_r (tests size by it). */
+size_t ecg_fr_sumcheck_tile(void);
+
+/* Binds x_0 .. x_(m-1) of a table to point[0 .. m-1] in that order (ark-poly's
+ * DenseMultilinearExtension::fix_variables; at m = log_n, evaluate):
+ *   d_out[i] = sum_{x < 2^m} eq(point, x) d_in[x + 2^m i],   i < 2^(log_n - m).
+ * point: host, m x 4 u64, Montgomery, < r; 1 <= m <= log_n.  One launch binds up to 11
+ * variables (registers, lane exchange, LDS) and later launches run on the workspace, so the
+ * table is read once.  At m = log_n value_out (host, 4 x u64; may be NULL otherwise) receives
+ * the value, the call synchronises and d_out may be NULL.  d_out must not overlap d_in.
+ * ECG_ML_OUT_CANONICAL: d_out and the value leave Montgomery form.  Errors as above.
+ * Workspace: 2^(log_n - 11) x 32 B ("fr_ml_fix_*"). */
+int ecg_fr_mle_fix_dev(ecg_ctx *ctx, int field_id, const void *d_in, uint32_t log_n,
+                       const uint64_t *point, uint32_t m, void *d_out, uint64_t *value_out,
+                       uint32_t flags, void *stream);
+
+/* The eq table of a zero-check: d_out[i] = scale prod_{j<log_n} (i_j ? r_j : 1 - r_j), r = point
+ * (host, log_n x 4 u64, Montgomery, < r); scale: host, Montgomery, < r, NULL = 1.  An outer
+ * product of two host-made factor tables of at most 2^16 entries over i = lo + 2^h hi: one
+ * product per element.  The call synchronises the stream (the factor tables' pinned staging
+ * is the next call's).  ECG_ML_OUT_CANONICAL: d_out leaves Montgomery form.  Errors as above.
+ * Workspace: at most 4 MB ("fr_ml_eq"). */
+int ecg_fr_eq_table_dev(ecg_ctx *ctx, int field_id, const uint64_t *point, uint32_t log_n,
+                        const uint64_t *scale, void *d_out, uint32_t flags, void *stream);
+
 /* ---- fixed-base batch scalar multiplication (G1) -----------------------------
  * out_i = s_i * B for n device-resident scalars and ONE base B: arkworks'
  * FixedBase::msm / batch_mul, the step that makes a structured reference

@@ -67,6 +67,12 @@ pub const ECG_GP_MAX_COLS: c_int = 4;
 pub const ECG_FRV_OUT_CANONICAL: c_int = 1;
 pub const ECG_FRV_MAX_TERMS: c_int = 8;
 
+// multilinear Fr (sumcheck round, bind, eq table): the limits of a round and the flag
+pub const ECG_SC_MAX_COLS: c_int = 8;
+pub const ECG_SC_MAX_PRODUCTS: c_int = 8;
+pub const ECG_SC_MAX_FACTORS: c_int = 4;
+pub const ECG_ML_OUT_CANONICAL: c_int = 1;
+
 // ecg_fixed_base_mul_dev flags
 pub const ECG_FB_SCALARS_MONTGOMERY: c_int = 1;
 
@@ -203,6 +209,19 @@ extern "C" {
                               index0: usize, d_out: *mut c_void, sum_out: *mut u64, flags: u32,
                               stream: *mut c_void) -> c_int;
     pub fn ecg_fr_lincomb_tile() -> usize;
+    // multilinear Fr: the sumcheck round polynomial (optionally fused with the last challenge's bind),
+    // fix_variables / evaluate, and the eq(r, .) table; tables pair the entries 2b and 2b + 1
+    pub fn ecg_fr_sumcheck_round_dev(ctx: *mut ecg_ctx, field_id: c_int, log_n: u32, k: u32,
+                                     d_cols: *const *const c_void, n_products: u32, factor_counts: *const u32,
+                                     factor_cols: *const u32, coeffs: *const u64, fold_r: *const u64,
+                                     d_folded: *const *mut c_void, evals_out: *mut u64, flags: u32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn ecg_fr_sumcheck_tile() -> usize;
+    pub fn ecg_fr_mle_fix_dev(ctx: *mut ecg_ctx, field_id: c_int, d_in: *const c_void, log_n: u32, point: *const u64,
+                              m: u32, d_out: *mut c_void, value_out: *mut u64, flags: u32,
+                              stream: *mut c_void) -> c_int;
+    pub fn ecg_fr_eq_table_dev(ctx: *mut ecg_ctx, field_id: c_int, point: *const u64, log_n: u32, scale: *const u64,
+                               d_out: *mut c_void, flags: u32, stream: *mut c_void) -> c_int;
 
     // ---- fixed-base batch scalar multiplication (arkworks FixedBase::msm) ----
     pub fn ecg_fixed_base_plan_info(curve_id: c_int, window_bits: u32, windows: *mut u32, row_entries: *mut u32,
